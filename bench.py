@@ -9,6 +9,11 @@ gradient all-reduce + SGD update), bs=16/GPU, synthetic COCO-shaped data, on N M
 Rank 0 prints ONE JSON line (see BASELINE.json for the metric).  `roofline` describes the dominant
 kernel class (the conv / wgrad class with the largest total time per step; since the head / CSP convs are grouped that is the grouped weight gradient), `cpu_baseline` the oracle
 (CPU fp32 restatement of the reference path) timed on this box's host cores on a bounded sample.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+
+also writes what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB), so that two builds run with
+the same arguments - identical seeded inputs and weights - can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -38,6 +43,32 @@ def synth_batch_device(B, H, W, seed, device, max_labels=100, num_classes=80, ma
         labels[b, :n, 1], labels[b, :n, 2] = cx, cy
         labels[b, :n, 3:5] = wh
     return images.to(device), labels.to(device)
+
+
+DUMP_BUDGET = 64 << 20     # bytes: --dump-outputs writes at most this much in all
+
+
+def seeded_sample(t, n, seed):
+    """host float32 copy of n elements of t (flattened) at positions fixed by (numel, n, seed), in ascending order; the
+    whole of t when it has at most n elements"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32"""
+    import numpy as np
+    arrs = {k: np.ascontiguousarray(v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, np.float32))
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET} byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def conv_algorithmic(d):
@@ -616,6 +647,9 @@ def bench_detr(args):
         last = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:       # (before the batch-7 loop below steps the model again)
+        dump_outputs(args.dump_outputs, dict(total_loss=last.reshape(1),
+                                             params_sample=seeded_sample(torch.cat([p.detach().reshape(-1) for p in params]), 1 << 22, seed=1)))
     # the reference's own per-GPU batch: IMS_PER_BATCH 56 on 8 GPUs = 7 (configs/coco/detr/detr_256_6_6_torchvision.yaml:26)
     bs7 = None
     if graphed and args.batch == 16 and os.environ.get("MI_BENCH_DETR_BS7", "1") == "1":
@@ -806,6 +840,9 @@ def bench_sparseinst(args):
         last = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(total_loss=last.reshape(1),
+                                             params_sample=seeded_sample(torch.cat([p.detach().reshape(-1) for p in params]), 1 << 22, seed=1)))
     ms, fl, byt = _time_conv(256, 256, B, S // 8, S // 8, 9)
     tf = fl / (ms * 1e-3) / 1e12
     out = {
@@ -951,6 +988,10 @@ step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed fr
     ap.add_argument("--no-h2d", action="store_true", help="skip the host-fed (PCIe-inclusive) measurement")
     ap.add_argument("--breakdown", type=str, default="", help="write the per-kernel-class breakdown JSON here")
     ap.add_argument("--config", type=str, default="yolox", help="yolox (the headline metric) | detr (BASELINE configs[3]) | sparseinst (configs[4], one GPU)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, 64 MB at most in all): "
+                         "yolox - the loss vector, the updated parameters, seeded samples of the raw head outputs and of the "
+                         "gradients; detr / sparseinst - the total loss and a seeded sample of the updated parameters")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) a few eager steps under rocprofv3 --pmc, no output")
     ap.add_argument("--trace-child", action="store_true", help="(internal) graph-replayed steps under rocprofv3 --kernel-trace, no output")
     args = ap.parse_args()
@@ -1014,6 +1055,12 @@ step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed fr
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     losses = trainer.losses(st)[:4].tolist()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, copied to the host before anything below steps this trainer again: the
+        # loss vector, the updated parameter arena (fp32, ~36 MB), fixed samples of the raw head outputs and the gradients
+        dump_outputs(args.dump_outputs, dict(losses=trainer.losses(st), params=trainer.params.data,
+                                             head_outputs_sample=seeded_sample(st["ps"].preds(), 1 << 21, seed=1),
+                                             grads_sample=seeded_sample(trainer.params.grad, 1 << 21, seed=2)))
     ms = dt / args.steps * 1e3
     value = args.batch * world * args.steps / dt
 

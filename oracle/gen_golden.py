@@ -360,6 +360,148 @@ def gold_random_perspective():
     print("random_perspective:", [len(res[f"labels{k}"]) for k in range(4)], "labels kept")
 
 
+def gold_random_perspective_warp():
+    """the reference's own random_perspective, whole (matrix, warp through the cv2 stand-in ref_loader installs, label
+    filter), on 240 x 320 images with the four fixed draws: the labels and the SHA-256 of the warped image"""
+    import hashlib
+    from gen_golden_inputs import PERSPECTIVE_DRAWS, synth_perspective_case
+    m = ref_loader.load_data_augment()
+    res = {}
+    orig_uniform = m.random.uniform
+    try:
+        for k, d in enumerate(PERSPECTIVE_DRAWS):
+            img, t = synth_perspective_case(100 + k, hw=(240, 320))
+            t[:, :4] *= 0.2
+            seq = list(d)
+            m.random.uniform = lambda a, b, _s=seq: _s.pop(0)
+            out, lab = m.random_perspective(img.copy(), t.copy(), degrees=10, translate=0.1, scale=(0.5, 1.5), shear=2.0,
+                                            border=[-img.shape[0] // 4, -img.shape[1] // 4])
+            out = np.ascontiguousarray(out)
+            res[f"labels{k}"], res[f"img_shape{k}"] = lab, np.array(out.shape)
+            res[f"img_dtype{k}"], res[f"img_sha256_{k}"] = np.array(str(out.dtype)), np.array(hashlib.sha256(out.tobytes()).hexdigest())
+    finally:
+        m.random.uniform = orig_uniform
+    np.savez_compressed(os.path.join(OUT, "random_perspective_warp.npz"), **res)
+    print("random_perspective_warp:", [len(res[f"labels{k}"]) for k in range(4)], "labels kept")
+
+
+def gold_export_traces():
+    """export mode of the reference's own modules (by path), for tests/test_export_onnx.py: the YOLOX-tiny and depthwise
+    outputs on seeded weights, and - for YOLOX-s, SparseInst and DETR - the operator census of the graph torch's exporter
+    traces from them at opset 11 and that graph's outputs, executed by tests/onnx_interp.py"""
+    import collections
+    import contextlib
+    import io
+    for p in (os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import onnx_interp as OI
+    import resnet_oracle as RO
+    from test_export_onnx import _torch_export
+    import yolov7_d2_amd as M
+    from yolov7_d2_amd import d2shim
+    from gen_golden_inputs import detr_onnx_weights, perturbed_bn_state_dict, sparseinst_onnx_weights, synth_sparseinst_images
+    res = {}
+
+    def census(name, data):
+        ct = collections.Counter(n[0] for n in OI.load(data)["nodes"])
+        res[f"{name}_ops"], res[f"{name}_counts"] = np.array(sorted(ct)), np.array([ct[k] for k in sorted(ct)], np.int64)
+        return OI.load(data)
+
+    for depth, width, depthwise, nc in ((0.33, 0.375, False, 80), (0.33, 0.5, True, 20)):
+        ref, _ = ref_loader.build_reference_yolox(depth, width, nc, seed=3, depthwise=depthwise)
+        sd, g = perturbed_bn_state_dict(O.init_state_dict(depth, width, nc, seed=3, depthwise=depthwise))
+        ref.load_state_dict(sd)
+        ref.eval()
+        ref.head.onnx_export = True
+        x = torch.rand(2, 96, 64, 3, generator=g) * 255
+        with torch.no_grad():
+            res[f"variant_{width}_{int(depthwise)}_{nc}"] = ref(x.permute(0, 3, 1, 2)).numpy()
+
+    ref, _ = ref_loader.build_reference_yolox(0.33, 0.5, 80, seed=0)
+    ref.load_state_dict(O.init_state_dict(0.33, 0.5, 80, seed=0))
+    ref.eval()
+    ref.head.onnx_export = True
+    imgs, _ = O.synth_batch(2, 64, 96, seed=11, max_gt=4)
+    with contextlib.redirect_stdout(io.StringIO()):
+        traced = _torch_export(ref, imgs, do_constant_folding=True, input_names=["images"], output_names=["outs"])
+    (res["yolox_out"],) = OI.run(census("yolox", traced), {"images": imgs.numpy()})
+
+    si, meta = ref_loader.load_sparseinst(), ref_loader.load_sparseinst_meta()
+    cfg = M.sparse_inst_r50_giam_cfg(device="cpu")
+    shapes = {n: types.SimpleNamespace(channels=c, stride=s) for n, c, s in (("res3", 512, 8), ("res4", 1024, 16), ("res5", 2048, 32))}
+
+    class RefSI(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.backbone = RO.R50Module(50, ("res3", "res4", "res5"))
+            self.encoder, self.decoder = si.encoder.InstanceContextEncoder(cfg, shapes), si.decoder.GroupIAMDecoder(cfg)
+            self.max_detections, self.mask_threshold = cfg.MODEL.SPARSE_INST.MAX_DETECTIONS, cfg.MODEL.SPARSE_INST.MASK_THRESHOLD
+            self.register_buffer("mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(1, 3, 1, 1))
+            self.register_buffer("std", torch.tensor(cfg.MODEL.PIXEL_STD).view(1, 3, 1, 1))
+
+        def forward(self, images):
+            x = (images.permute(0, 3, 1, 2) - self.mean) / self.std
+            out = self.decoder(self.encoder(self.backbone(x)))
+            return meta.SparseInst.inference_onnx(self, out, images, x.shape[2:])
+
+    ref = RefSI()
+    ref.load_state_dict(sparseinst_onnx_weights({k: v.shape for k, v in ref.state_dict().items() if k not in ("mean", "std")}), strict=False)
+    ref.eval()
+    img = synth_sparseinst_images(1, 64, 96, 600)
+    with contextlib.redirect_stdout(io.StringIO()):
+        traced = _torch_export(ref, img, do_constant_folding=True, input_names=["images"], output_names=["masks", "scores", "labels"])
+    masks, res["sparseinst_scores"], res["sparseinst_labels"] = OI.run(census("sparseinst", traced), {"images": img.numpy()})
+    res["sparseinst_mask_shape"], res["sparseinst_masks"] = np.array(masks.shape), np.packbits(masks, axis=-1)
+
+    ref_loader.load()
+    det = ref_loader.load_detr()
+    det.build_backbone = lambda c: RO.R50Module(50, c.MODEL.RESNETS.OUT_FEATURES, c.MODEL.RESNETS.STRIDE_IN_1X1)
+    det.ImageList, det.Instances, det.Boxes = d2shim.ImageList, d2shim.Instances, d2shim.Boxes
+    torch.manual_seed(0)
+    ref = det.Detr(M.detr_r50_cfg(device="cpu"))
+    ref.load_state_dict(detr_onnx_weights({k: v.shape for k, v in ref.state_dict().items()}), strict=False)
+    ref.eval()
+    ref.onnx_export = True
+    x = synth_sparseinst_images(2, 64, 96, 905).permute(0, 3, 1, 2).contiguous()
+    # torchvision is a stub here (ref_loader): during a trace the real one answers _is_tracing() == True, which sends
+    # nested_tensor_from_tensor_list to its no-padding export variant (utils/misc.py:88-92, 174-184)
+    tv = sys.modules["torchvision"]
+    keep_tracing = tv._is_tracing
+    tv._is_tracing = lambda: True
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            traced = _torch_export(ref, x, do_constant_folding=True, input_names=["images"], output_names=["outs"])
+    finally:
+        tv._is_tracing = keep_tracing
+    (res["detr_out"],) = OI.run(census("detr", traced), {"images": x.numpy()})
+    np.savez_compressed(os.path.join(OUT, "export_traces.npz"), **res)
+    print("export_traces:", {k: v.shape for k, v in res.items()})
+
+
+def gold_nms_native():
+    """the reference's own native greedy NMS (deploy/trt_cc/demo_yolox.cc, built into oracle/_ref/ by oracle/Makefile) on
+    the tie-free cases of tests/test_ref_nms.py: kept indices, single class and class by class"""
+    import subprocess
+    import ref_nms as R
+    from gen_golden_inputs import (NATIVE_BATCHED_CPU_CASES, NATIVE_BATCHED_GPU_CASES, NATIVE_NMS_CASES,
+                                   synth_tie_free_nms_case)
+    if not R.available():
+        subprocess.run(["make", "-C", HERE], check=True)
+    res = {}
+    for n, thr in NATIVE_NMS_CASES:
+        boxes, scores, _ = synth_tie_free_nms_case(n, 1, thr, seed=n)
+        res[f"nms_{n}_{thr}"] = R.nms_xyxy(boxes, scores, thr)
+    for n, ncls, thr in [(n, ncls, 0.65) for n, ncls in NATIVE_BATCHED_CPU_CASES]:
+        boxes, scores, idxs = synth_tie_free_nms_case(n, ncls, thr, seed=7 * n)
+        res[f"batched_{n}_{ncls}_{thr}"] = R.batched_nms_xyxy(boxes, scores, idxs, thr)
+    for n, ncls, thr in NATIVE_BATCHED_GPU_CASES:
+        boxes, scores, idxs = synth_tie_free_nms_case(n, ncls, thr, seed=3 * n + ncls)
+        res[f"batched_{n}_{ncls}_{thr}"] = R.batched_nms_xyxy(boxes, scores, idxs, thr)
+    np.savez_compressed(os.path.join(OUT, "nms_native.npz"), **res)
+    print("nms_native:", {k: len(v) for k, v in res.items()})
+
+
 def gold_distortion():
     """the reference's own YOLOFDistortTransform.apply_image (data/transforms/transform.py:250-308) on seeded uint8 images
     with numpy's global stream seeded: the distorted image (float32 in the reference; stored as uint8 - same integers) and
@@ -1009,6 +1151,9 @@ if __name__ == "__main__":
     gold_yolov6_loss()
     gold_bifpn()
     gold_random_perspective()
+    gold_random_perspective_warp()
+    gold_nms_native()
+    gold_export_traces()
     gold_distortion()
     gold_pil_resize()
     gold_jpeg()

@@ -234,6 +234,67 @@ def synth_nms_case(n, ncls, seed, spread=14.0):
     return boxes, scores, idxs
 
 
+# the reference's native greedy NMS (oracle/ref_nms.py) on these cases is stored in nms_native.npz (tests/test_ref_nms.py)
+NATIVE_NMS_CASES = [(1, 0.45), (2, 0.45), (64, 0.45), (65, 0.65), (300, 0.65), (1000, 0.65), (1500, 0.3)]     # (n, thr), seed n
+NATIVE_BATCHED_CPU_CASES = [(500, 5), (900, 80), (1200, 80)]                                     # (n, ncls), thr 0.65, seed 7 n
+NATIVE_BATCHED_GPU_CASES = [(1, 1, 0.45), (63, 1, 0.45), (64, 3, 0.45), (65, 80, 0.65), (1000, 80, 0.65), (3000, 80, 0.65),
+                            (8400, 80, 0.65)]                                                    # (n, ncls, thr), seed 3 n + ncls
+
+
+def synth_tie_free_nms_case(n, ncls, thr, seed):
+    """clustered boxes with unique scores and no pairwise IoU within 2e-4 of the threshold (the reference computes the
+    areas from (w, h), the torchvision form from (x2 - x1): at an exact tie the float roundings could differ) - boxes of
+    a near-threshold pair are dropped, so slightly fewer than n come back"""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    ctr = g.uniform(40, 600, size=(max(n // 25, 1), 2))
+    c = ctr[g.integers(0, len(ctr), n)] + g.normal(0, 12, size=(n, 2))
+    wh = g.uniform(20, 120, size=(n, 2))
+    boxes = np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32)
+    scores = (g.permutation(n).astype(np.float32) / n * 0.98 + 0.01).astype(np.float32)
+    idxs = g.integers(0, ncls, n)
+    x1 = np.maximum(boxes[:, None, 0], boxes[None, :, 0]); y1 = np.maximum(boxes[:, None, 1], boxes[None, :, 1])
+    x2 = np.minimum(boxes[:, None, 2], boxes[None, :, 2]); y2 = np.minimum(boxes[:, None, 3], boxes[None, :, 3])
+    inter = np.clip(x2 - x1, 0, None) * np.clip(y2 - y1, 0, None)
+    area = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
+    iou = inter / (area[:, None] + area[None, :] - inter)
+    near = np.abs(iou - thr) <= 2e-4
+    drop = np.unique(np.nonzero(np.triu(near, 1))[1])
+    keep = np.setdiff1d(np.arange(n), drop)
+    assert len(keep) >= max(1, n - n // 10)
+    return boxes[keep], scores[keep], idxs[keep]
+
+
+def perturbed_bn_state_dict(sd, seed=5):
+    """a copy of sd whose BatchNorms have running statistics and affine parameters that are not the identity, drawn in
+    key order -> (state_dict, generator); the generator goes on to draw the caller's inputs"""
+    g = torch.Generator().manual_seed(seed)
+    sd = dict(sd)
+    for k in list(sd):
+        if k.endswith(".running_mean"):
+            p, n = k[: -len("running_mean")], sd[k].numel()
+            sd[p + "running_mean"] = torch.randn(n, generator=g) * 0.1
+            sd[p + "running_var"] = 0.5 + torch.rand(n, generator=g)
+            sd[p + "weight"] = 0.5 + torch.rand(n, generator=g)
+            sd[p + "bias"] = torch.randn(n, generator=g) * 0.1
+    return sd, g
+
+
+# four fixed sequences of the random.uniform draws random_perspective makes, in the order it makes them
+PERSPECTIVE_DRAWS = [(3.7, 0.8, 1.2, -0.7, 0.45, 0.55), (-9.5, 1.45, -2.0, 2.0, 0.6, 0.4), (0.0, 1.0, 0.0, 0.0, 0.5, 0.5),
+                     (10.0, 0.5, 0.3, 0.1, 0.41, 0.59)]
+
+
+def synth_perspective_case(seed, n=12, hw=(1200, 1400)):
+    """a uint8 HWC image and n label rows (x1, y1, x2, y2, class) as float64"""
+    import numpy as np
+    r = np.random.RandomState(seed)
+    img = r.randint(0, 256, (hw[0], hw[1], 3), dtype=np.uint8)
+    x1 = r.uniform(0, hw[1] - 50, n); y1 = r.uniform(0, hw[0] - 50, n)
+    t = np.stack([x1, y1, x1 + r.uniform(3, 400, n), y1 + r.uniform(3, 400, n), r.randint(0, 80, n).astype(np.float64)], 1)
+    return img, t
+
+
 def synth_mask_case(n, H, W, ncls, seed):
     """n binary masks (overlapping blobs), descending scores, labels: the inputs of matrix_nms"""
     g = torch.Generator().manual_seed(seed)

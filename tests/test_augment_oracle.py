@@ -1,6 +1,7 @@
-"""CPU: the input-pipeline oracle (oracle/augment_oracle.py).  Label / matrix logic against the reference's own
-random_perspective run by path (when /root/reference is present) and against the committed golden; the restated OpenCV
-pixel arithmetic through properties OpenCV's definitions imply (identity, integer shifts, constant images, border)."""
+"""CPU: the input-pipeline oracle (oracle/augment_oracle.py).  Label / matrix logic against the committed goldens of the
+reference's own random_perspective run by path (oracle/gen_golden.py); the restated OpenCV pixel arithmetic through
+properties OpenCV's definitions imply (identity, integer shifts, constant images, border)."""
+import hashlib
 import os
 import random
 
@@ -8,18 +9,7 @@ import numpy as np
 import pytest
 
 import augment_oracle as A
-import ref_loader
-
-
-def _case(seed, n=12, hw=(1200, 1400)):
-    r = np.random.RandomState(seed)
-    img = r.randint(0, 256, (hw[0], hw[1], 3), dtype=np.uint8)
-    x1 = r.uniform(0, hw[1] - 50, n); y1 = r.uniform(0, hw[0] - 50, n)
-    t = np.stack([x1, y1, x1 + r.uniform(3, 400, n), y1 + r.uniform(3, 400, n), r.randint(0, 80, n).astype(np.float64)], 1)
-    return img, t
-
-
-DRAWS = [(3.7, 0.8, 1.2, -0.7, 0.45, 0.55), (-9.5, 1.45, -2.0, 2.0, 0.6, 0.4), (0.0, 1.0, 0.0, 0.0, 0.5, 0.5), (10.0, 0.5, 0.3, 0.1, 0.41, 0.59)]
+from gen_golden_inputs import PERSPECTIVE_DRAWS as DRAWS, synth_perspective_case as _case
 
 
 def test_random_perspective_labels_against_golden(golden_dir):
@@ -34,20 +24,19 @@ def test_random_perspective_labels_against_golden(golden_dir):
         assert (w, h) == tuple(g[f"wh{k}"])
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
-def test_random_perspective_against_reference_by_path(monkeypatch):
-    m = ref_loader.load_data_augment()
+def test_random_perspective_against_reference_by_path(golden_dir):
+    """the whole call against the reference's random_perspective run by path with the same draws
+    (random_perspective_warp.npz: its labels and the SHA-256 of its warped image)"""
+    g = np.load(os.path.join(golden_dir, "random_perspective_warp.npz"))
     for k, d in enumerate(DRAWS):
         img, t = _case(100 + k, hw=(240, 320))
         t[:, :4] *= 0.2
         border = [-img.shape[0] // 4, -img.shape[1] // 4]
-        seq = list(d)
-        monkeypatch.setattr(m.random, "uniform", lambda a, b, _s=seq: _s.pop(0))
-        ref_img, ref_t = m.random_perspective(img.copy(), t.copy(), degrees=10, translate=0.1, scale=(0.5, 1.5), shear=2.0,
-                                              border=border)
         got_img, got_t = A.random_perspective(img.copy(), t.copy(), d, border)
-        assert np.array_equal(ref_t, got_t)
-        assert np.array_equal(ref_img, got_img)                   # (same warp restatement on both sides: pins the call, not cv2)
+        assert np.array_equal(g[f"labels{k}"], got_t)
+        got_img = np.ascontiguousarray(got_img)                   # (same warp restatement on both sides: pins the call, not cv2)
+        assert got_img.shape == tuple(g[f"img_shape{k}"]) and str(got_img.dtype) == str(g[f"img_dtype{k}"])
+        assert hashlib.sha256(got_img.tobytes()).hexdigest() == str(g[f"img_sha256_{k}"])
 
 
 def test_resize_properties():

@@ -101,69 +101,56 @@ def test_exported_yolox_graph_reproduces_the_references_export_mode_output(golde
         export_yolox_onnx(model, io.BytesIO(), 64, 96)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/yolov7"), reason="the reference tree only exists in the build container")
 @pytest.mark.parametrize("depth,width,depthwise,nc", [(0.33, 0.375, False, 80), (0.33, 0.5, True, 20)], ids=["tiny", "depthwise_20cls"])
-def test_exported_variants_against_the_reference_run_by_path(depth, width, depthwise, nc):
+def test_exported_variants_against_the_reference_run_by_path(depth, width, depthwise, nc, golden_dir):
     """other widths (YOLOX-tiny, BASELINE configs[0]) and MODEL.DARKNET.DEPTH_WISE: the exported graph against the
-    reference's own modules (loaded by path) in export mode, with BatchNorm running statistics that are not the identity"""
-    import ref_loader
+    reference's own modules (run by path in export mode: export_traces.npz) on seeded weights with BatchNorm running
+    statistics that are not the identity"""
     import yolov7_d2_amd as M
+    import yolox_oracle as O
+    from gen_golden_inputs import perturbed_bn_state_dict
     from yolov7_d2_amd.export_onnx import export_yolox_onnx
-    ref, _ = ref_loader.build_reference_yolox(depth, width, nc, seed=3, depthwise=depthwise)
-    g = torch.Generator().manual_seed(5)
-    for m in ref.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.running_mean.copy_(torch.randn(m.num_features, generator=g) * 0.1)
-            m.running_var.copy_(0.5 + torch.rand(m.num_features, generator=g))
-            m.weight.data.copy_(0.5 + torch.rand(m.num_features, generator=g))
-            m.bias.data.copy_(torch.randn(m.num_features, generator=g) * 0.1)
-    ref.eval()
-    ref.head.onnx_export = True
+    sd, g = perturbed_bn_state_dict(O.init_state_dict(depth, width, nc, seed=3, depthwise=depthwise))
     cfg = M.yolox_s_cfg(device="cpu")
     cfg.MODEL.YOLO.DEPTH_MUL, cfg.MODEL.YOLO.WIDTH_MUL, cfg.MODEL.YOLO.CLASSES = depth, width, nc
     cfg.MODEL.DARKNET.DEPTH_WISE = depthwise
     model = M.build_model(cfg)
-    missing = model.load_state_dict(ref.state_dict(), strict=False)
+    missing = model.load_state_dict(sd, strict=False)
     assert not missing.missing_keys, missing.missing_keys[:5]
     data = export_yolox_onnx(model.eval(), io.BytesIO(), height=96, width=64)
     x = torch.rand(2, 96, 64, 3, generator=g) * 255
     (out,) = OI.run(OI.load(data), {"images": x.numpy()})
-    with torch.no_grad():
-        want = ref(x.permute(0, 3, 1, 2)).numpy()
+    want = np.load(os.path.join(golden_dir, "export_traces.npz"))[f"variant_{width}_{int(depthwise)}_{nc}"]
     assert out.shape == want.shape == (2, 126, 6 + nc)
     keep = [c for c in range(6 + nc) if c != 5]
     np.testing.assert_allclose(out[..., keep], want[..., keep], rtol=5e-4, atol=5e-4)
     assert (out[..., 5] == want[..., 5]).mean() > 0.97
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/yolov7"), reason="the reference tree only exists in the build container")
-def test_written_graph_equals_the_file_torchs_exporter_traces_from_the_reference():
-    """what export.py itself would write: the REFERENCE's modules (by path, head.onnx_export = True) traced by torch's
-    TorchScript exporter at opset 11 with constant folding - against the graph this package writes from its module tree
-    with the same weights: the same operator census where it matters (83 Conv, 80 Sigmoid, 76 Mul, 8 Add, 3 MaxPool, 2
-    Resize, no BatchNormalization in either) and the same output when both files are executed"""
+def _traced_census(gold, name):
+    """operator census of a graph torch's exporter traced from the reference's modules (export_traces.npz)"""
     import collections
-    import contextlib
-    import ref_loader
+    return collections.Counter(dict(zip([str(k) for k in gold[f"{name}_ops"]], [int(v) for v in gold[f"{name}_counts"]])))
+
+
+def test_written_graph_equals_the_file_torchs_exporter_traces_from_the_reference(golden_dir):
+    """what export.py itself would write: the REFERENCE's modules (by path, head.onnx_export = True) traced by torch's
+    TorchScript exporter at opset 11 with constant folding (its operator census and executed output: export_traces.npz,
+    oracle/gen_golden.py::gold_export_traces) - against the graph this package writes from its module tree with the same
+    weights: the same operator census where it matters (83 Conv, 80 Sigmoid, 76 Mul, 8 Add, 3 MaxPool, 2 Resize, no
+    BatchNormalization in either) and the same output when both files are executed"""
+    import collections
     import yolox_oracle as O
     from yolov7_d2_amd.export_onnx import export_yolox_onnx
-    ref, _ = ref_loader.build_reference_yolox(0.33, 0.5, 80, seed=0)
-    ref.load_state_dict(O.init_state_dict(0.33, 0.5, 80, seed=0))
-    ref.eval()
-    ref.head.onnx_export = True
+    gold = np.load(os.path.join(golden_dir, "export_traces.npz"))
     imgs, _ = O.synth_batch(2, 64, 96, seed=11, max_gt=4)
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            traced = _torch_export(ref, imgs, do_constant_folding=True, input_names=["images"], output_names=["outs"])
-    except Exception as e:       # noqa: BLE001
-        pytest.skip("torch's exporter is unavailable here: %r" % (e,))
     model, _ = _model()
     mine = export_yolox_onnx(model, io.BytesIO(), height=64, width=96)
-    gt, gm = OI.load(traced), OI.load(mine)
-    ct, cm = collections.Counter(n[0] for n in gt["nodes"]), collections.Counter(n[0] for n in gm["nodes"])
+    gm = OI.load(mine)
+    ct, cm = _traced_census(gold, "yolox"), collections.Counter(n[0] for n in gm["nodes"])
     for op in ("Conv", "Sigmoid", "Mul", "Add", "MaxPool", "Resize", "Exp", "ArgMax", "Split", "BatchNormalization"):
         assert ct[op] == cm[op], (op, ct[op], cm[op])
-    (a,) = OI.run(gt, {"images": imgs.numpy()})                                   # the traced file takes NCHW (the meta-arch's
+    a = gold["yolox_out"]                                                         # the traced file took NCHW (the meta-arch's
     (b,) = OI.run(gm, {"images": imgs.permute(0, 2, 3, 1).contiguous().numpy()})  # preprocess_input permute sits outside `ref`)
     keep = [c for c in range(86) if c != 5]
     np.testing.assert_allclose(b[..., keep], a[..., keep], rtol=2e-4, atol=2e-4)
@@ -278,56 +265,27 @@ def test_exported_sparseinst_graph_reproduces_the_references_export_mode_outputs
         export_sparseinst_onnx(model, io.BytesIO(), H, W)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/yolov7"), reason="the reference tree only exists in the build container")
-def test_written_sparseinst_graph_equals_the_trace_of_the_references_modules():
+def test_written_sparseinst_graph_equals_the_trace_of_the_references_modules(golden_dir):
     """what export.py itself would write for the part of the model the reference tree contains: its InstanceContextEncoder
-    + GroupIAMDecoder + inference_onnx (loaded by path), traced by torch's exporter under is_in_onnx_export() at opset 11,
-    against the graph this package writes - same operator census where it matters, same outputs when both are executed
-    (the traced module takes the ResNet restatement as its backbone)"""
+    + GroupIAMDecoder + inference_onnx (loaded by path), traced by torch's exporter under is_in_onnx_export() at opset 11
+    (census and executed outputs: export_traces.npz, oracle/gen_golden.py::gold_export_traces), against the graph this
+    package writes - same operator census where it matters, same outputs when both are executed (the traced module took
+    the ResNet restatement as its backbone)"""
     import collections
-    import contextlib
-    import types
-    import ref_loader
-    import resnet_oracle as RO
-    import yolov7_d2_amd as M
-    from gen_golden_inputs import sparseinst_onnx_weights, synth_sparseinst_images
+    from gen_golden_inputs import synth_sparseinst_images
     from yolov7_d2_amd.export_onnx import export_sparseinst_onnx
-    si, meta = ref_loader.load_sparseinst(), ref_loader.load_sparseinst_meta()
-    cfg = M.sparse_inst_r50_giam_cfg(device="cpu")
-    shapes = {n: types.SimpleNamespace(channels=c, stride=s) for n, c, s in (("res3", 512, 8), ("res4", 1024, 16), ("res5", 2048, 32))}
-
-    class Ref(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.backbone = RO.R50Module(50, ("res3", "res4", "res5"))
-            self.encoder, self.decoder = si.encoder.InstanceContextEncoder(cfg, shapes), si.decoder.GroupIAMDecoder(cfg)
-            self.max_detections, self.mask_threshold = cfg.MODEL.SPARSE_INST.MAX_DETECTIONS, cfg.MODEL.SPARSE_INST.MASK_THRESHOLD
-            self.register_buffer("mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(1, 3, 1, 1))
-            self.register_buffer("std", torch.tensor(cfg.MODEL.PIXEL_STD).view(1, 3, 1, 1))
-
-        def forward(self, images):
-            x = (images.permute(0, 3, 1, 2) - self.mean) / self.std
-            out = self.decoder(self.encoder(self.backbone(x)))
-            return meta.SparseInst.inference_onnx(self, out, images, x.shape[2:])
-
-    ref = Ref()
-    sd = sparseinst_onnx_weights({k: v.shape for k, v in ref.state_dict().items() if k not in ("mean", "std")})
-    ref.load_state_dict(sd, strict=False)
-    ref.eval()
+    gold = np.load(os.path.join(golden_dir, "export_traces.npz"))
     H, W = 64, 96
     img = synth_sparseinst_images(1, H, W, 600)
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            traced = _torch_export(ref, img, do_constant_folding=True, input_names=["images"], output_names=["masks", "scores", "labels"])
-    except Exception as e:       # noqa: BLE001
-        pytest.skip("torch's exporter is unavailable here: %r" % (e,))
     mine = export_sparseinst_onnx(_sparseinst_model(), io.BytesIO(), height=H, width=W)
-    gt, gm = OI.load(traced), OI.load(mine)
-    ct, cm = collections.Counter(n[0] for n in gt["nodes"]), collections.Counter(n[0] for n in gm["nodes"])
+    gm = OI.load(mine)
+    ct, cm = _traced_census(gold, "sparseinst"), collections.Counter(n[0] for n in gm["nodes"])
     for op in ("Conv", "Relu", "MaxPool", "MatMul", "TopK", "ArgMax", "ReduceMax", "Greater", "Sqrt", "Resize", "BatchNormalization"):
         assert ct[op] == cm[op], (op, ct[op], cm[op])
     assert ct["AveragePool"] == 3 and cm["AveragePool"] == 4      # (the 1 x 1 window of the 6-bin stage on a 2 x 3 map: the tracer drops the identity)
-    ta, tb, tc = OI.run(gt, {"images": img.numpy()})
+    shape = tuple(int(v) for v in gold["sparseinst_mask_shape"])
+    ta = np.unpackbits(gold["sparseinst_masks"], axis=-1)[..., : shape[-1]].astype(bool)
+    tb, tc = gold["sparseinst_scores"], gold["sparseinst_labels"]
     ma, mb, mc = OI.run(gm, {"images": img.numpy()})
     assert ta.shape == ma.shape and tb.shape == mb.shape and tc.shape == mc.shape
     miss, worst = _match_rows(mb[0], mc[0], ma[0], tb[0], tc[0], ta[0])
@@ -384,52 +342,27 @@ def test_sine_position_embedding_constant_equals_the_oracle():
         np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/yolov7"), reason="the reference tree only exists in the build container")
-def test_written_detr_graph_equals_the_trace_of_the_references_detr():
+def test_written_detr_graph_equals_the_trace_of_the_references_detr(golden_dir):
     """what export.py would write if its detr branch ran: the REFERENCE's Detr (by path, onnx_export = True; its own
     MaskedBackboneTraceFriendly mask resize, PositionEmbeddingSine cumsums, nn.MultiheadAttention, heads and export rows)
-    traced by torch's exporter at opset 11 - against the graph this package writes from its module tree: the same census
-    of the operators that carry the model and, executed, the same output"""
+    traced by torch's exporter at opset 11 (census and executed output: export_traces.npz,
+    oracle/gen_golden.py::gold_export_traces) - against the graph this package writes from its module tree: the same
+    census of the operators that carry the model and, executed, the same output"""
     import collections
-    import contextlib
-    import ref_loader
-    import resnet_oracle as R
-    from gen_golden_inputs import detr_onnx_weights, synth_sparseinst_images
-    from yolov7_d2_amd import d2shim, detr_r50_cfg
+    from gen_golden_inputs import synth_sparseinst_images
     from yolov7_d2_amd.export_onnx import export_detr_onnx
-    ref_loader.load()
-    det = ref_loader.load_detr()
-    det.build_backbone = lambda cfg: R.R50Module(50, cfg.MODEL.RESNETS.OUT_FEATURES, cfg.MODEL.RESNETS.STRIDE_IN_1X1)
-    det.ImageList, det.Instances, det.Boxes = d2shim.ImageList, d2shim.Instances, d2shim.Boxes
-    torch.manual_seed(0)
-    ref = det.Detr(detr_r50_cfg(device="cpu"))
-    ref.load_state_dict(detr_onnx_weights({k: v.shape for k, v in ref.state_dict().items()}), strict=False)
-    ref.eval()
-    ref.onnx_export = True
+    gold = np.load(os.path.join(golden_dir, "export_traces.npz"))
     H, W = 64, 96
     x = synth_sparseinst_images(2, H, W, 905).permute(0, 3, 1, 2).contiguous()
-    # torchvision is a stub here (ref_loader): during a trace the real one answers _is_tracing() == True, which sends
-    # nested_tensor_from_tensor_list to its no-padding export variant (utils/misc.py:88-92, 174-184); the eager variant's
-    # slice assignment into the mask does not survive tracing (an all-True mask is folded in: NaN out of the first softmax)
-    tv = sys.modules["torchvision"]
-    keep_tracing = tv._is_tracing
-    tv._is_tracing = lambda: True
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            traced = _torch_export(ref, x, do_constant_folding=True, input_names=["images"], output_names=["outs"])
-    except Exception as e:       # noqa: BLE001
-        pytest.skip("torch's exporter is unavailable here: %r" % (e,))
-    finally:
-        tv._is_tracing = keep_tracing
     mine = export_detr_onnx(_detr_model(), io.BytesIO(), height=H, width=W)
-    gt, gm = OI.load(traced), OI.load(mine)
-    ct, cm = collections.Counter(n[0] for n in gt["nodes"]), collections.Counter(n[0] for n in gm["nodes"])
+    gm = OI.load(mine)
+    ct, cm = _traced_census(gold, "detr"), collections.Counter(n[0] for n in gm["nodes"])
     for op in ("Conv", "Relu", "MaxPool", "Softmax", "Sigmoid", "ArgMax", "ReduceMax", "BatchNormalization"):
         assert ct[op] == cm[op], (op, ct[op], cm[op])
     # LayerNorms (2 ReduceMean each): 2 per encoder layer, 3 per decoder layer, decoder.norm - which the trace keeps for all six
     # intermediate levels although only hs[-1] reaches the output (dead nodes); the written graph has the live one
     assert ct["ReduceMean"] == 2 * (12 + 18 + 6) and cm["ReduceMean"] == 2 * (12 + 18 + 1)
-    (a,) = OI.run(gt, {"images": x.numpy()})
+    a = gold["detr_out"]
     (b,) = OI.run(gm, {"images": x.numpy()})
     assert a.shape == b.shape == (2, 100, 6) and not np.isnan(a).any()
     np.testing.assert_allclose(b[..., :5], a[..., :5], rtol=1e-4, atol=2e-5)

@@ -63,8 +63,18 @@ def test_detr_yaml_builds_the_reference_state_dict():
     assert all(abs(ref.criterion.weight_dict[k] - model.criterion.weight_dict[k]) < 1e-12 for k in ref.criterion.weight_dict)
 
 
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(REF_CFG, "sparseinst", "*.yaml"))))
+# configs/coco/sparseinst/ of the reference: a fixed list, so that the cases (their full paths, as a glob of the folder
+# would give them) are the same whether or not the tree is on the machine
+SPARSEINST_YAMLS = ["Base-SparseInst.yaml", "sparse_inst_r50_base.yaml", "sparse_inst_r50_dcn_giam_aug.yaml",
+                    "sparse_inst_r50_giam.yaml", "sparse_inst_r50_giam_aug.yaml", "sparse_inst_r50vd_base.yaml",
+                    "sparse_inst_r50vd_dcn_giam.yaml", "sparse_inst_r50vd_dcn_giam_aug.yaml", "sparse_inst_r50vd_giam.yaml",
+                    "sparse_inst_r50vd_giam_aug.yaml"]
+
+
+@pytest.mark.parametrize("path", [os.path.join(REF_CFG, "sparseinst", name) for name in SPARSEINST_YAMLS])
 def test_sparseinst_yamls_merge(path):
+    # every yaml of the folder is a case: one added to the reference would not go untested
+    assert sorted(os.path.basename(f) for f in glob.glob(os.path.join(REF_CFG, "sparseinst", "*.yaml"))) == sorted(SPARSEINST_YAMLS)
     cfg = M.get_yolox_cfg(path, ["MODEL.DEVICE", "cpu"])
     if os.path.basename(path).startswith("Base-"):
         assert cfg.MODEL.META_ARCHITECTURE == "SparseInst"
