@@ -775,6 +775,20 @@ int mi_batched_nms(const float* boxes, const float* scores, const float* idxs, i
  * its fixed-point iteration over the IoU matrix converges to the greedy result. */
 int mi_batched_nms_ex(const float* boxes, const float* scores, const float* idxs, int n, float iou_thr, int arithmetic,
                       int32_t* order, uint64_t* mask, float* sboxes, int64_t* keep, int32_t* n_keep, mi_stream_t s);
+/* YOLOX eval postprocess (utils/boxes.py:171-210) for a whole batch in one fixed launch sequence, with no host sync, no
+ * allocation and no memset (graph-capturable).  pred [B][A][ld] fp32 decoded (cx,cy,w,h,obj,cls[C],...), ld >= 5 + C: its
+ * first four columns are rewritten IN PLACE to x1,y1,x2,y2 (the reference's side effect).  Per image: anchors with
+ * obj * max(cls) >= conf_thr are the candidates (ascending anchor order), NMS as mi_batched_nms (its arithmetic chosen per
+ * image by the image's candidate count), and the kept rows (x1,y1,x2,y2,obj,cls_conf,cls_idx) go to dets[b][0 .. counts[b])
+ * of dets [B][A][7] in descending score order; rows past counts[b] are left as they were.  B <= 1024 per call,
+ * 1 <= A <= 65536, C >= 1.  ws: >= mi_yolox_postprocess_ws_bytes(B, A, C) bytes, 8-byte aligned; the size is the worst
+ * case, every anchor a candidate:
+ *   B * (8 * A * ceil(A / 64) + 72 * A + 4 * ceil(A / 256) + 8)
+ * where the first term is the suppression bitmask: ~142 MB at B = 16, A = 8400 and ~318 MB at B = 16, A = 12600.
+ * _ws_bytes returns a negative MI_E* code for arguments outside those limits. */
+int64_t mi_yolox_postprocess_ws_bytes(int B, int A, int C);
+int mi_yolox_postprocess(float* pred, int B, int A, int C, int ld, float conf_thr, float nms_thr, float* dets,
+                         int32_t* counts, void* ws, int64_t ws_bytes, mi_stream_t s);
 /* class-aware Soft-NMS (batched_softnms, meta_arch/utils.py:33-63): scores are rescaled IN PLACE, keep[] receives the
  * indices with score > score_threshold in descending score order (ties: ascending index).  sigma is the reference's
  * iou_threshold argument; linear 0 = "gaussian" exp(-iou^2 / sigma), 1 = "linear".  n <= 16384. */

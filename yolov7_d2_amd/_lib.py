@@ -361,6 +361,8 @@ _PROTOS = {
                                        C.c_uint64, _vp]),
     "mi_iou_loss_v6": (C.c_int, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "mi_batched_nms": (C.c_int, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi_yolox_postprocess": (C.c_int, [_vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i64, _vp]),
+    "mi_yolox_postprocess_ws_bytes": (C.c_int64, [_i, _i, _i]),
     "mi_abi_sizeof": (C.c_int, [_i]),
     "mi_sigmoid_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "mi_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i64, _f, _vp]),

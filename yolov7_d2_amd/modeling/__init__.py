@@ -1,5 +1,5 @@
 from .blocks import BaseConv, Bottleneck, CSPLayer, Focus, SPPBottleneck
-from .postprocess import (batched_nms, postprocess, generalized_batched_nms, batched_softnms, batched_clusternms,
+from .postprocess import (batched_nms, postprocess, postprocess_batched, generalized_batched_nms, batched_softnms, batched_clusternms,
                           matrix_nms, mask_nms)
 from .yolox import YOLOX
 from .yolox_net import CSPDarknet, YOLOPAFPN, YOLOXHead, build_cspdarknetx_backbone

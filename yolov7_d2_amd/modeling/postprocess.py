@@ -1,6 +1,9 @@
 """Eval post-processing: `postprocess` of yolov7/utils/boxes.py:171-210 with the NMS on the GPU
-(libmi355det mi_batched_nms, torchvision.ops.batched_nms semantics)."""
+(libmi355det mi_batched_nms, torchvision.ops.batched_nms semantics).  `postprocess_batched` does the whole batch in one
+fixed launch sequence (mi_yolox_postprocess); `postprocess` is that plus one read-back of the B counts
+(MI_POSTPROCESS_BATCHED=0: the per-image loop, `_postprocess_per_image`)."""
 import ctypes as C
+import os
 
 import torch
 
@@ -31,10 +34,67 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
     return keep[: int(nkeep.item())]
 
 
+_PP_WS = {}          # (device index, B, A, C) -> workspace of mi_yolox_postprocess
+_PP_MAX_B = 1024     # images per mi_yolox_postprocess call
+
+
+def _pp_workspace(dev, B, A, C):
+    key = (dev.index, B, A, C)
+    ws = _PP_WS.get(key)
+    if ws is None:
+        nbytes = L.check(L.lib().mi_yolox_postprocess_ws_bytes(B, A, C), "mi_yolox_postprocess_ws_bytes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _PP_WS[key] = ws
+    return ws
+
+
+def postprocess_batched(prediction, num_classes, conf_thre=0.7, nms_thre=0.45):
+    """`postprocess` for all B images at once on the device, with no host sync: prediction [B, A, 5+ncls] decoded,
+    fp32, contiguous, on the GPU (its first four columns are rewritten to x1,y1,x2,y2 in place, like `postprocess`) ->
+    (dets [B, A, 7], counts [B] int32): image b's detections are dets[b, :counts[b]], the rows `postprocess` returns
+    for it, in the same order and bit for bit.  Rows past counts[b] are unspecified.  The workspace (worst case, every
+    anchor a candidate: ~150 MB at B = 16, A = 8400) is cached per (device, B, A, num_classes)."""
+    if not prediction.is_cuda:
+        raise L.MI355Error("postprocess_batched: HIP tensors required (no CPU fallback)")
+    if prediction.dtype != torch.float32 or not prediction.is_contiguous() or prediction.dim() != 3:
+        raise ValueError("postprocess_batched: prediction must be a contiguous float32 [B, A, 5 + num_classes] tensor "
+                         f"(got {prediction.dtype}, shape {tuple(prediction.shape)}, contiguous={prediction.is_contiguous()})")
+    B, A, ld = prediction.shape
+    if num_classes < 1 or ld < 5 + num_classes:
+        raise ValueError(f"postprocess_batched: {ld} columns cannot hold 5 + {num_classes} classes")
+    dev = prediction.device
+    dets = torch.empty(B, A, 7, dtype=torch.float32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return dets, counts
+    if A == 0:
+        counts.zero_()
+        return dets, counts
+    for b0 in range(0, B, _PP_MAX_B):
+        nb = min(_PP_MAX_B, B - b0)
+        ws = _pp_workspace(dev, nb, A, num_classes)
+        L.check(L.lib().mi_yolox_postprocess(prediction[b0].data_ptr(), nb, A, num_classes, ld, float(conf_thre),
+                                             float(nms_thre), dets[b0].data_ptr(), counts[b0:].data_ptr(),
+                                             ws.data_ptr(), ws.numel(), L.stream_ptr()), "mi_yolox_postprocess")
+    return dets, counts
+
+
 def postprocess(prediction, num_classes, conf_thre=0.7, nms_thre=0.45):
     """prediction [B, A, 5+ncls] decoded (cx,cy,w,h,obj,cls...) -> list of [n_i, 7] or None
     rows (x1,y1,x2,y2,obj,cls_conf,cls_idx) in descending score order; mutates `prediction` like the
-    reference does (cxcywh -> xyxy in place)."""
+    reference does (cxcywh -> xyxy in place).  A contiguous float32 GPU prediction goes through
+    `postprocess_batched` (one read-back: the counts); other layouts and dtypes, and MI_POSTPROCESS_BATCHED=0, take the
+    per-image loop, which also runs its NMS on the GPU."""
+    batched = (os.environ.get("MI_POSTPROCESS_BATCHED", "1") != "0" and prediction.is_cuda
+               and prediction.dtype == torch.float32 and prediction.is_contiguous() and prediction.dim() == 3)
+    if not batched:
+        return _postprocess_per_image(prediction, num_classes, conf_thre, nms_thre)
+    dets, counts = postprocess_batched(prediction, num_classes, conf_thre, nms_thre)
+    return [dets[b, :n] if n else None for b, n in enumerate(counts.tolist())]
+
+
+def _postprocess_per_image(prediction, num_classes, conf_thre=0.7, nms_thre=0.45):
+    """the reference's per-image loop (utils/boxes.py:171-210) in torch ops + batched_nms: two host syncs per image"""
     box_corner = prediction.new_empty(prediction.shape)
     box_corner[:, :, 0] = prediction[:, :, 0] - prediction[:, :, 2] / 2
     box_corner[:, :, 1] = prediction[:, :, 1] - prediction[:, :, 3] / 2
