@@ -985,9 +985,9 @@ enum {
   MI_OP_DECODE = 23,
   MI_OP_PACK_W_BATCH = 24,
   MI_OP_WGRAD_GROUP = 25,
-  MI_OP_STREAM = 26, /* i[0] = stream id for the following commands (0 = the caller's stream, 1..MI_MAX_AUX = aux) */
-  MI_OP_FORK = 27,   /* aux stream i[0] waits for everything issued so far on the caller's stream               */
-  MI_OP_JOIN = 28,   /* the caller's stream waits for everything issued so far on aux stream i[0]               */
+  MI_OP_RESERVED26 = 26, /* was STREAM: every command runs on the caller's stream */
+  MI_OP_RESERVED27 = 27, /* was FORK */
+  MI_OP_RESERVED28 = 28, /* was JOIN */
   MI_OP_BIAS_GRADS = 29,
   MI_OP_CONV_GROUP = 30,   /* p0 = mi_conv_group* (host), p1 = device job table */
   MI_OP_BN_GROUP = 31,     /* p0 = mi_bn_group* (host),   p1 = device job table */
@@ -1001,20 +1001,7 @@ enum {
   MI_OP_COUNT
 };
 
-/* Independent chains (e.g. the three FPN levels of the YOLOX head) may be issued on auxiliary HIP streams owned by
- * the library (STREAM / FORK / JOIN commands): under hipGraph capture they become parallel branches of the graph,
- * which the MI355X runs concurrently (measured: two 64-block chains overlap ~2x). */
-#define MI_MAX_AUX 4
 int mi_cmdlist_run(const mi_cmd* cmds, int n, mi_stream_t s);
-/* A HIP stream whose kernels run only on the compute units of `mask` (hipExtStreamCreateWithCUMask; nwords 32-bit words,
- * bit i of the mask = logical CU i; on the 8-XCD MI355X the driver deals logical CUs round-robin over the XCDs, so the low
- * 64 bits are 8 CUs of EVERY XCD - measured with the census probe of include/mi355_debug.h).  The caller owns the stream
- * (mi_stream_destroy).  Used for the weight-gradient side queue beside the backward chain (engine.NativeTrainer). */
-int mi_stream_create_cu_mask(const uint32_t* mask, int nwords, mi_stream_t* out);
-int mi_stream_destroy(mi_stream_t s);
-/* replace auxiliary stream `sid` (1..MI_MAX_AUX) of the executor's STREAM / FORK / JOIN commands by a caller-owned stream
- * (NULL: back to the library's own); takes effect for command lists run or captured afterwards */
-int mi_aux_stream_set(int sid, mi_stream_t s);
 /* returns an opaque handle (>0) or <0 */
 int64_t mi_graph_capture(const mi_cmd* cmds, int n, mi_stream_t s);
 int mi_graph_launch(int64_t handle, mi_stream_t s);

@@ -84,7 +84,7 @@ def _members(plan, builder, k):
             out += [c for c in by_tag[t] if c.op == L.OP["WGRAD"]]
         return out
     arr, _ = plan.bwd_cmds
-    if L.OPS[arr[k].op] in ("FORK", "JOIN", "STREAM", "NOP"):
+    if L.OPS[arr[k].op] == "NOP":
         return []
     merged = plan.cmd_members["bwd"][k]
     if merged is not None:                       # a merged launch: the builder commands it was made of (merges nest)

@@ -4,7 +4,7 @@ of graph-replayed steps, tools/gpu_trace.sh) with gpurun_out/tags.txt (tools/dum
 usage: trace_steps.py <tag> [--warm]   (--warm: per (kernel, shape) the fastest instance and the excess of the others)"""
 import collections, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NDISP = {"STREAM": 0, "LOSS_FWD": 4, "LOSS_BWD_FUSED": 2, "WGRAD_GROUP": None}
+NDISP = {"LOSS_FWD": 4, "LOSS_BWD_FUSED": 2, "WGRAD_GROUP": None}
 
 
 def load(tag):

@@ -18,8 +18,6 @@ MI_CONV_BNBWD = 4
 MI_CONV_OUT_F32 = 2
 MI_BN_BAR_WORDS = 64 * (1 + 2 * 16)
 MI_BN_SLOTS = 16
-MI_MAX_AUX = 4
-MI_WGRAD_STREAM = MI_MAX_AUX   # the last auxiliary stream is created with the lowest priority (background work)
 
 
 class MI355Error(RuntimeError):
@@ -224,7 +222,7 @@ class mi_cmd(C.Structure):
 # opcode names must match the enum in include/mi355_det.h
 OPS = ["NOP", "CONV", "WGRAD", "PACK_W", "RESERVED4", "RESERVED5", "BN_ACT_FWD", "BN_BWD_REDUCE",
        "RESERVED8", "BN_BWD_APPLY", "FOCUS", "UPSAMPLE_FWD", "UPSAMPLE_BWD", "SPP_FWD", "SPP_BWD", "COPY",
-       "COLSUM", "LOSS_FWD", "LOSS_BWD", "SPLIT_DPREDS", "MEMSET", "SGD", "BN_EVAL_AFFINE", "DECODE", "PACK_W_BATCH", "WGRAD_GROUP", "STREAM", "FORK", "JOIN", "BIAS_GRADS",
+       "COLSUM", "LOSS_FWD", "LOSS_BWD", "SPLIT_DPREDS", "MEMSET", "SGD", "BN_EVAL_AFFINE", "DECODE", "PACK_W_BATCH", "WGRAD_GROUP", "RESERVED26", "RESERVED27", "RESERVED28", "BIAS_GRADS",
        "CONV_GROUP", "BN_GROUP", "SPLIT_DPREDS_BATCH", "BN_BWD_FUSED", "DWCONV_FWD", "DWCONV_DGRAD", "DWCONV_WGRAD",
        "LOSS_BWD_FUSED"]
 OP = {n: k for k, n in enumerate(OPS)}
@@ -370,8 +368,6 @@ _PROTOS = {
     "mi_pos_embed_sine": (C.c_int, [_vp, _i, _i, _i, _i, _f, _i, _f, _i, _vp, _vp]),
     "mi_sgd_momentum_step": (C.c_int, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp]),
     "mi_cmdlist_run": (C.c_int, [C.POINTER(mi_cmd), _i, _vp]),
-    "mi_stream_create_cu_mask": (C.c_int, [C.POINTER(C.c_uint32), _i, C.POINTER(C.c_void_p)]),
-    "mi_stream_destroy": (C.c_int, [_vp]),
     "mi_upload_async": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mi_pyramid_pool_fwd": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "mi_pyramid_pool_bwd": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
@@ -382,7 +378,6 @@ _PROTOS = {
     "mi_padding_masks": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mi_normalize_pad_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "mi_mask_targets_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mi_aux_stream_set": (C.c_int, [_i, _vp]),
     "mi_graph_capture": (C.c_int64, [C.POINTER(mi_cmd), _i, _vp]),
     "mi_graph_launch": (C.c_int, [_i64, _vp]),
     "mi_graph_destroy": (C.c_int, [_i64]),
@@ -425,8 +420,6 @@ def dbg():
         D = C.CDLL(path)
         D.mi_debug_code_polluter.restype = C.c_int
         D.mi_debug_code_polluter.argtypes = [_i, _i, _vp]
-        D.mi_debug_cu_census.restype = C.c_int
-        D.mi_debug_cu_census.argtypes = [_vp, _i, _i, _vp]
         _dbg = D
     return _dbg
 

@@ -34,22 +34,3 @@ extern "C" int mi_debug_code_polluter(int kb, int blocks, mi_dbg_stream_t st) {
   MI_CHECK_LAUNCH("code_polluter");
   return MI_OK;
 }
-
-// ---- CU census: which (XCC, SE, CU) each block of a launch lands on
-__global__ __launch_bounds__(256) void cu_census_kernel(uint32_t* out, long long spin_ticks) {
-  uint32_t xcc, hw;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  const long long t0 = wall_clock64();
-  while (wall_clock64() - t0 < spin_ticks) __builtin_amdgcn_s_sleep(8);
-  if (threadIdx.x == 0) {
-    out[2 * blockIdx.x] = xcc & 0xf;
-    out[2 * blockIdx.x + 1] = hw;
-  }
-}
-extern "C" int mi_debug_cu_census(uint32_t* out, int blocks, int spin_us, mi_dbg_stream_t st) {
-  if (!out || blocks <= 0) MI_FAIL(MI_EINVAL, "cu_census: args");
-  hipLaunchKernelGGL(cu_census_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)st, out, (long long)spin_us * 100);  // 100 MHz
-  MI_CHECK_LAUNCH("cu_census");
-  return MI_OK;
-}

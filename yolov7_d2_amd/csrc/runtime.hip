@@ -115,55 +115,11 @@ static int run_one(const mi_cmd& c, hipStream_t s) {
   }
 }
 
-// auxiliary streams / events for parallel chains (created once, never destroyed: process lifetime)
-static hipStream_t g_aux[MI_MAX_AUX];
-static hipEvent_t g_ev_fork[MI_MAX_AUX], g_ev_join[MI_MAX_AUX];
-static bool g_aux_ready = false;
-static hipStream_t g_aux_user[MI_MAX_AUX] = {nullptr, nullptr, nullptr, nullptr};   // caller-owned replacements (mi_aux_stream_set)
-static inline hipStream_t aux_stream(int k) { return g_aux_user[k] ? g_aux_user[k] : g_aux[k]; }
-static int ensure_aux() {
-  if (g_aux_ready) return MI_OK;
-  int prio_least = 0, prio_greatest = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  for (int k = 0; k < MI_MAX_AUX; ++k) {
-    // the LAST auxiliary stream carries background work (weight gradients beside the backward chain): lowest priority,
-    // so that the chain's workgroups are dispatched first whenever both have blocks pending
-    const hipError_t e = (k == MI_MAX_AUX - 1)
-                             ? hipStreamCreateWithPriority(&g_aux[k], hipStreamNonBlocking, prio_least)
-                             : hipStreamCreateWithFlags(&g_aux[k], hipStreamNonBlocking);
-    if (e != hipSuccess) MI_FAIL(MI_ELAUNCH, "aux stream");
-    if (hipEventCreateWithFlags(&g_ev_fork[k], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g_ev_join[k], hipEventDisableTiming) != hipSuccess)
-      MI_FAIL(MI_ELAUNCH, "aux event");
-  }
-  g_aux_ready = true;
-  return MI_OK;
-}
-
 extern "C" int mi_cmdlist_run(const mi_cmd* cmds, int n, mi_stream_t st) {
   if (mi_device_count() <= 0) MI_FAIL(MI_ENODEV, "no HIP device");
   hipStream_t s = (hipStream_t)st;
-  hipStream_t cur = s;
   for (int k = 0; k < n; ++k) {
-    const int op = cmds[k].op;
-    if (op == MI_OP_STREAM || op == MI_OP_FORK || op == MI_OP_JOIN) {
-      const int sid = cmds[k].i[0];
-      if (sid < 0 || sid > MI_MAX_AUX) MI_FAIL(MI_EINVAL, "cmd %d: stream id %d", k, sid);
-      if (sid > 0 && ensure_aux() != MI_OK) return MI_ELAUNCH;
-      if (op == MI_OP_STREAM) {
-        cur = sid ? aux_stream(sid - 1) : s;
-      } else if (sid > 0 && op == MI_OP_FORK) {
-        if (hipEventRecord(g_ev_fork[sid - 1], s) != hipSuccess ||
-            hipStreamWaitEvent(aux_stream(sid - 1), g_ev_fork[sid - 1], 0) != hipSuccess)
-          MI_FAIL(MI_ELAUNCH, "cmd %d: fork", k);
-      } else if (sid > 0) {
-        if (hipEventRecord(g_ev_join[sid - 1], aux_stream(sid - 1)) != hipSuccess ||
-            hipStreamWaitEvent(s, g_ev_join[sid - 1], 0) != hipSuccess)
-          MI_FAIL(MI_ELAUNCH, "cmd %d: join", k);
-      }
-      continue;
-    }
-    const int rc = run_one(cmds[k], cur);
+    const int rc = run_one(cmds[k], s);
     if (rc != MI_OK) {
       char tmp[400];
       snprintf(tmp, sizeof(tmp), "%s", g_mi_err);
@@ -178,32 +134,6 @@ extern "C" int mi_upload_async(void* dst_dev, const void* src_pinned, int64_t nb
   MI_REQUIRE(dst_dev && src_pinned && nbytes > 0, "upload_async: args");
   const hipError_t e = hipMemcpyAsync(dst_dev, src_pinned, (size_t)nbytes, hipMemcpyHostToDevice, (hipStream_t)st);
   if (e != hipSuccess) MI_FAIL(MI_ELAUNCH, "upload_async: %s", hipGetErrorString(e));
-  return MI_OK;
-}
-
-// ---- CU-masked streams (the weight-gradient side queue)
-extern "C" int mi_stream_create_cu_mask(const uint32_t* mask, int nwords, mi_stream_t* out) {
-  if (mi_device_count() <= 0) MI_FAIL(MI_ENODEV, "no HIP device");
-  MI_REQUIRE(mask && out && nwords > 0 && nwords <= 32, "stream_create_cu_mask: args");
-  bool any = false;
-  for (int k = 0; k < nwords; ++k) any = any || mask[k] != 0;
-  MI_REQUIRE(any, "stream_create_cu_mask: empty mask");
-  hipStream_t s = nullptr;
-  const hipError_t e = hipExtStreamCreateWithCUMask(&s, (uint32_t)nwords, mask);
-  if (e != hipSuccess || !s) MI_FAIL(MI_ELAUNCH, "hipExtStreamCreateWithCUMask: %s", hipGetErrorString(e));
-  *out = (mi_stream_t)s;
-  return MI_OK;
-}
-extern "C" int mi_stream_destroy(mi_stream_t st) {
-  MI_REQUIRE(st, "stream_destroy: null");
-  for (int k = 0; k < MI_MAX_AUX; ++k)
-    if (g_aux_user[k] == (hipStream_t)st) g_aux_user[k] = nullptr;
-  if (hipStreamDestroy((hipStream_t)st) != hipSuccess) MI_FAIL(MI_ELAUNCH, "hipStreamDestroy failed");
-  return MI_OK;
-}
-extern "C" int mi_aux_stream_set(int sid, mi_stream_t st) {
-  MI_REQUIRE(sid >= 1 && sid <= MI_MAX_AUX, "aux_stream_set: stream id %d", sid);
-  g_aux_user[sid - 1] = (hipStream_t)st;
   return MI_OK;
 }
 

@@ -202,24 +202,23 @@ class YOLOXHead(_NoEager):
         nch = 5 + self.num_classes
         a0 = 0
         # the FPN levels - and inside a level the classification and the regression branch - are independent chains
-        # (yolox_head.py:160-172 loops over them): the plan zips them into grouped launches (Plan._group_lanes), or, with
-        # MI_MULTI_STREAM, runs the small levels on auxiliary streams
+        # (yolox_head.py:160-172 loops over them): the plan zips them into grouped launches (Plan._group_lanes)
         b = ctx.b
         stems = []
         b.par_begin(tag + ".stems")
         for k, x in enumerate(fpn_outs):
-            with b.on_stream(k), b.on_lane(k):
+            with b.on_lane(k):
                 stems.append(self.stems[k].emit(ctx, x, f"{tag}.stems.{k}"))
         b.par_end(tag + ".stems")
         b.par_begin(tag + ".levels")
         for k, x in enumerate(fpn_outs):
             t = stems[k]
-            with b.on_stream(k), b.on_lane(2 * k):
+            with b.on_lane(2 * k):
                 c = self.cls_convs[k][0].emit(ctx, t, f"{tag}.cls_convs.{k}.0")
                 c = self.cls_convs[k][1].emit(ctx, c, f"{tag}.cls_convs.{k}.1")
                 b.pred_conv(f"{tag}.cls_preds.{k}", c, self.cls_preds[k].weight, self.cls_preds[k].bias,
                             ctx.g(self.cls_preds[k].weight), ctx.g(self.cls_preds[k].bias), preds, A, a0, 5, nch)
-            with b.on_stream(k), b.on_lane(2 * k + 1):
+            with b.on_lane(2 * k + 1):
                 r = self.reg_convs[k][0].emit(ctx, t, f"{tag}.reg_convs.{k}.0")
                 r = self.reg_convs[k][1].emit(ctx, r, f"{tag}.reg_convs.{k}.1")
                 fused = self._reg_obj_views(ctx, k)

@@ -87,20 +87,6 @@ def plan_buckets(total_elems, writes, n_buckets, bounds=None):
     return res
 
 
-def parallel_regions(plan):
-    """[(first, last)] command index ranges of the FORK .. JOIN regions of the backward list (never cut inside)"""
-    arr, n = plan.bwd_cmds
-    regs, start = [], None
-    for k in range(n):
-        op = arr[k].op
-        if op == L.OP["FORK"] and start is None:
-            start = k
-        if op == L.OP["JOIN"] and (k + 1 >= n or arr[k + 1].op != L.OP["JOIN"]):
-            regs.append((start, k))
-            start = None
-    return regs
-
-
 class GradReducer:
     """all-reduce(sum) of flat-gradient buckets, launched as soon as each bucket is complete; the 1/world
     scaling is folded into the optimizer update (grad_scale)."""
@@ -111,15 +97,11 @@ class GradReducer:
         self.pending = []
         self.enabled = True      # False: skip the collectives (bench.py measures the exposed communication time that way)
 
-    def segments(self, n_cmds, regions=()):
-        """[(cmd_lo, cmd_hi, bucket or None)]: run cmds [lo,hi) then reduce the bucket.  A cut that would fall inside a
-        multi-stream region (FORK .. JOIN) moves to the end of the region."""
+    def segments(self, n_cmds):
+        """[(cmd_lo, cmd_hi, bucket or None)]: run cmds [lo,hi) then reduce the bucket"""
         segs, prev = [], 0
         for (lo, hi, last) in self.buckets:
             cut = max(prev, last + 1)
-            for (r0, r1) in regions:
-                if r0 < cut <= r1:
-                    cut = r1 + 1
             segs.append((prev, cut, (lo, hi)))
             prev = cut
         if prev < n_cmds:

@@ -80,9 +80,8 @@ class _Ptr:
 
 
 class _Cmd:
-    def __init__(self, op, i=(), f=(), p=(), l=(), desc=None, tag="", stream=0):
+    def __init__(self, op, i=(), f=(), p=(), l=(), desc=None, tag=""):
         self.op, self.i, self.f, self.p, self.l, self.desc, self.tag = op, list(i), list(f), list(p), list(l), desc, tag
-        self.stream = stream   # 0 = caller's stream, k > 0 = auxiliary stream k (inside a parallel region)
         self.lane = 0          # index of the independent chain (inside a parallel region) this command belongs to
 
 
@@ -161,12 +160,8 @@ class PlanBuilder:
         self.device = torch.device(device)
         # all weight gradients in one grouped launch at the end of backward (each layer keeps its own dy buffer)
         self.group_wgrad = (os.environ.get("MI_WGRAD_GROUP", "1") != "0") if group_wgrad is None else group_wgrad
-        # independent chains (the head's FPN levels) on auxiliary streams -> parallel hipGraph branches
-        # measured (A/B, round 1): the branches do overlap (tools/micro/graph_branches.hip: 2x on long kernels) but with
-        # ~300 short kernels in the region the step gets 3 % SLOWER (every node of a multi-branch graph pays extra
-        # dependency handling) -> opt-in only
-        self.multi_stream = os.environ.get("MI_MULTI_STREAM", "0") != "0" and self.group_wgrad
-        self.cur_stream = 0
+        # every command runs on the caller's stream: the head's FPN levels as parallel hipGraph branches measured 3 %
+        # slower and the option was removed (docs/DESIGN_rounds_1_3.md, tools/micro/graph_branches.hip)
         self.cur_lane = 0
         # the independent chains of a parallel region (the head's FPN levels) zipped into grouped launches: one
         # CONV_GROUP / BN_GROUP per chain position instead of one launch per level
@@ -187,12 +182,6 @@ class PlanBuilder:
         # Three buckets: [neck + head] on the wire under the whole backbone, [dark4 + dark5] under dark3 .. stem, only the
         # last (stem .. dark3, 2.4 MB of the 35.9) is exposed.
         self.wgrad_stages = [("head.", "neck."), ("backbone.dark5.", "backbone.dark4.")]
-        # MI_WGRAD_ASYNC=G: the weight gradients run as G grouped launches on an auxiliary LOW-PRIORITY stream (a parallel
-        # hipGraph branch), each issued as soon as the last of its layers' out-gradients exists, so that their blocks
-        # fill the CUs the latency-bound backward chain of ~200 small kernels leaves idle.  The branch joins before the
-        # optimizer.  The groups are cut from the backward-ordered layer list at equal shares of the weight-gradient
-        # FLOPs (head first, stem last).
-        self.wgrad_async = int(os.environ.get("MI_WGRAD_ASYNC", "0") or 0)
         self.csp_lanes = os.environ.get("MI_CSP_LANES", "1") != "0"   # CSP conv1 / conv2 as lanes (see blocks.CSPLayer)
         self.training = training            # build the backward command list
         self.bn_train = training if bn_train is None else bn_train  # batch statistics vs running statistics
@@ -272,8 +261,7 @@ class PlanBuilder:
 
     # ---------------------------------------------------------------- command emission
     def emit(self, op, i=(), f=(), p=(), l=(), desc=None, tag="", prologue=False):
-        c = _Cmd(L.OP[op], i, f, [x if isinstance(x, _Ptr) else _Ptr(x) for x in p], l, desc, tag,
-                 stream=0 if prologue else self.cur_stream)
+        c = _Cmd(L.OP[op], i, f, [x if isinstance(x, _Ptr) else _Ptr(x) for x in p], l, desc, tag)
         c.lane = 0 if prologue else self.cur_lane
         if self._emitting_bwd:
             self.bwd.append(c)
@@ -285,13 +273,12 @@ class PlanBuilder:
 
     def on_backward(self, fn):
         if self.training:
-            self.bwd_gens.append((fn, self.cur_stream, self.cur_lane))
+            self.bwd_gens.append((fn, self.cur_lane))
 
     # ---------------------------------------------------------------- parallel regions
     def par_begin(self, tag="par"):
-        """start of a region whose commands carry stream ids (see `on_stream`); everything before the region is visible
-        to every stream of the region (FORK), everything in it is visible after `par_end` (JOIN).  The backward list
-        gets the mirrored region automatically."""
+        """start of a region of independent chains (see `on_lane`), marked by a NOP that Plan._group_lanes consumes.  The
+        backward list gets the mirrored region automatically."""
         self.emit("NOP", tag=tag + ".begin")
         self.on_backward(lambda: self.emit("NOP", tag=tag + ".end"))
 
@@ -299,22 +286,9 @@ class PlanBuilder:
         self.emit("NOP", tag=tag + ".end")
         self.on_backward(lambda: self.emit("NOP", tag=tag + ".begin"))
 
-    def on_stream(self, sid):
-        b = self
-
-        class _Ctx:
-            def __enter__(self_):
-                self_.prev, self_.prev_lane = b.cur_stream, b.cur_lane
-                b.cur_stream = sid if b.multi_stream else 0
-                b.cur_lane = sid
-
-            def __exit__(self_, *a):
-                b.cur_stream, b.cur_lane = self_.prev, self_.prev_lane
-        return _Ctx()
-
     def on_lane(self, lane):
         """commands emitted inside belong to independent chain `lane` of the enclosing parallel region (see
-        Plan._group_lanes); unlike on_stream this never changes the stream"""
+        Plan._group_lanes)"""
         b = self
 
         class _Ctx:
@@ -696,10 +670,10 @@ class PlanBuilder:
     def finalize(self, materialize=True):
         # backward command generation, reverse order of forward emission
         self._emitting_bwd = True
-        for fn, sid, lane in reversed(self.bwd_gens):
-            self.cur_stream, self.cur_lane = sid, lane
+        for fn, lane in reversed(self.bwd_gens):
+            self.cur_lane = lane
             fn()
-        self.cur_stream = self.cur_lane = 0
+        self.cur_lane = 0
         self._emitting_bwd = False
         self.bwd_gens = []
         for which, lst in (("fwd", self.fwd), ("bwd", self.bwd)):
@@ -741,7 +715,8 @@ class Plan:
             buf.base = base
         self.descs = []
         self.cmd_descs = {}
-        self.fwd_cmds, self.fwd_tags = self._materialize(self._overlap_prologue(self._batch_packs(b.prologue), list(b.fwd)), "fwd")
+        # (the weight pack and Focus as two graph branches measured 1.7 % slower, the option was removed: DESIGN.md §10)
+        self.fwd_cmds, self.fwd_tags = self._materialize(self._batch_packs(b.prologue) + b.fwd, "fwd")
         self.graphs = {}
         # BatchNorm backward as one fused launch per layer or as reduce + apply: MI_BN_FUSED=1 / 0, default "auto" = both
         # backward lists are captured and timed ON THIS DEVICE and the faster one is kept.  (Measured: on most boxes of the
@@ -761,27 +736,6 @@ class Plan:
                         (L.OPS[self.bwd_cmds[0][k].op] == "BN_GROUP" and self.bwd_cmds[0][k].i[0] == 3)
                         for k in range(self.bwd_cmds[1]))):
             self._select_bn_backward()
-
-    @staticmethod
-    def _overlap_prologue(pro, fwd):
-        """the weight re-pack (reads the fp32 masters, writes the bf16 images: ~54 MB, 45 us) and the Focus packer (reads the
-        uint8 batch, writes the stem's input: ~125 MB, 49 us) depend on nothing of each other and both stream; MI_PACK_ASYNC=1
-        issues them as two branches of the captured graph, joined by the first convolution.  OPT-IN: measured SLOWER - 5.50 vs
-        5.41 ms per step, four alternating pairs (profiles/r04_pack_async_ab.txt): one fork / join inside the hipGraph costs
-        more than the ~45 us the overlap can save, like the head's branch experiment of round 1 (-3 %)."""
-        if os.environ.get("MI_PACK_LATE", "0") == "1" and len(pro) == 1 and pro[0].op == L.OP["PACK_W_BATCH"]:
-            # (A/B, round 6: the Focus packer takes 13 - 20 us alone and 41 us right behind the weight pack - does it matter who
-            #  follows the pack?  Order: Focus, pack, stem convolution)
-            k = next((i for i, c in enumerate(fwd) if c.op == L.OP["FOCUS"]), None)
-            if k is not None and all(c.op in (L.OP["MEMSET"], L.OP["FOCUS"]) for c in fwd[: k + 1]):
-                return fwd[: k + 1] + pro + fwd[k + 1:]
-        if os.environ.get("MI_PACK_ASYNC", "0") != "1" or len(pro) != 1 or pro[0].op != L.OP["PACK_W_BATCH"]:
-            return pro + fwd
-        k = next((i for i, c in enumerate(fwd) if c.op == L.OP["FOCUS"]), None)
-        if k is None or any(c.op not in (L.OP["MEMSET"], L.OP["FOCUS"]) for c in fwd[: k + 1]):
-            return pro + fwd
-        pro[0].stream = 1
-        return [_Cmd(L.OP["NOP"], tag="prologue.begin")] + pro + fwd[: k + 1] + [_Cmd(L.OP["NOP"], tag="prologue.end")] + fwd[k + 1:]
 
     def check_bn_barriers(self):
         """raise if any grid barrier of the one-launch BatchNorm backward gave up since the last check (word 2 of a
@@ -866,8 +820,6 @@ class Plan:
         self.wgrad_descs = []
         if not (b.group_wgrad and len(wg) >= 2):
             return bwd
-        if getattr(b, "wgrad_async", 0) > 0 and not b.wgrad_split:
-            return self._async_wgrads(bwd, wg, b.wgrad_async)
         stages, rest = [], list(wg)
         if b.wgrad_split:
             for pre in b.wgrad_stages:
@@ -889,41 +841,6 @@ class Plan:
                 out.append(self._wgrad_group_cmd(stages[si], "wgrad_group.early" if si == 0 else f"wgrad_group.stage{si}"))
         out.append(self._wgrad_group_cmd(rest, "wgrad_group"))
         self.wgrad_stage_tags = [[c.tag for c in st] for st in stages] + [[c.tag for c in rest]]
-        return out
-
-    def _async_wgrads(self, bwd, wg, G):
-        """G weight-gradient groups on auxiliary stream MI_WGRAD_STREAM (see PlanBuilder.wgrad_async).  Group g is
-        issued right after the backward command that produces the last out-gradient of its layers: FORK (the aux stream
-        waits for everything issued so far), the grouped launch on the aux stream, back to the caller's stream.  The
-        groups serialise on the aux stream (they share the split-K workspace); one JOIN at the end of the list."""
-        sid = L.MI_WGRAD_STREAM
-        def flops(c):
-            d = c.desc
-            return 2.0 * d.N * d.outH * d.outW * d.CoutPad * d.CinPad * len(d.taps)
-        tot = sum(flops(c) for c in wg)
-        groups, cur, acc = [], [], 0.0
-        for c in wg:                       # backward order: head ... stem
-            cur.append(c)
-            acc += flops(c)
-            if acc >= tot * (len(groups) + 1) / G and len(groups) < G - 1:
-                groups.append(cur)
-                cur = []
-        if cur:
-            groups.append(cur)
-        groups = [g for g in groups if g]
-        last = {}
-        for gi, g in enumerate(groups):
-            last[max(i for i, c in enumerate(bwd) if any(c is w for w in g))] = gi
-        out = []
-        for i, c in enumerate(bwd):
-            if c.op != L.OP["WGRAD"]:
-                out.append(c)
-            if i in last:
-                gi = last[i]
-                grp = self._wgrad_group_cmd(groups[gi], f"wgrad_group.async{gi}") if len(groups[gi]) >= 2 else groups[gi][0]
-                out += [_Cmd(L.OP["FORK"], i=[sid], tag=f"wgrad.fork{gi}"), _Cmd(L.OP["STREAM"], i=[sid], tag="wgrad.stream"),
-                        grp, _Cmd(L.OP["STREAM"], i=[0], tag="wgrad.stream0")]
-        out.append(_Cmd(L.OP["JOIN"], i=[sid], tag="wgrad.join"))
         return out
 
     def _wgrad_group_cmd(self, wg, tag):
@@ -954,11 +871,7 @@ class Plan:
 
     def _fuse_bn_bwd_pairs(self, bwd):
         """BN_BWD_REDUCE + BN_BWD_APPLY of one layer -> ONE launch that keeps (da, y) in registers across a grid-wide
-        barrier (mi_bn_act_bwd_fused): 3 tensor passes instead of 5.  Not with auxiliary streams: two fused launches running
-        concurrently would each wait for blocks the other keeps from starting."""
-        b = self.b
-        if b.multi_stream or getattr(b, "wgrad_async", 0) > 0:
-            return bwd
+        barrier (mi_bn_act_bwd_fused): 3 tensor passes instead of 5."""
         RED, APP = L.OP["BN_BWD_REDUCE"], L.OP["BN_BWD_APPLY"]
         out, k = [], 0
         while k < len(bwd):
@@ -966,7 +879,7 @@ class Plan:
             n = bwd[k + 1] if k + 1 < len(bwd) else None
             if (c.op == RED and n is not None and n.op == APP and c.tag.endswith(".bnred")
                     and n.tag == c.tag[:-len(".bnred")] + ".bnapply" and len(n.p) > 12 and n.p[12].obj is not None):
-                f = _Cmd(L.OP["BN_BWD_FUSED"], i=n.i, l=n.l, p=n.p, tag=c.tag[:-len(".bnred")] + ".bnbwd", stream=n.stream)
+                f = _Cmd(L.OP["BN_BWD_FUSED"], i=n.i, l=n.l, p=n.p, tag=c.tag[:-len(".bnred")] + ".bnbwd")
                 f.lane = n.lane
                 f.members = [c, n]
                 out.append(f)
@@ -988,7 +901,7 @@ class Plan:
         spec = ConvSpec(kind="split_jobs", jobs=[dict(dst=c.p[1], a0=c.i[3], HW=c.i[4], c0=c.i[5], nc=c.i[6], ld=c.i[7])
                                                  for c in sp])
         cmd = _Cmd(L.OP["SPLIT_DPREDS_BATCH"], i=[B, A, nch, len(sp)], p=[_Ptr(None), sp[0].p[0]], desc=spec,
-                   tag="loss.split_all", stream=bwd[at].stream)
+                   tag="loss.split_all")
         cmd.lane = bwd[at].lane
         cmd.members = list(sp)
         rest = [c for c in bwd if c.op != L.OP["SPLIT_DPREDS"]]
@@ -1019,7 +932,7 @@ class Plan:
         keep = os.environ.get("MI_LOSS_DPREDS", "0") == "1"
         cmd = _Cmd(L.OP["LOSS_BWD_FUSED"], i=[len(sp.desc.jobs), len(bg.desc.jobs)], l=[bg.p[2].obj.nbytes // 4], desc=lb.desc,
                    p=[_Ptr(None), lb.p[1], lb.p[2] if keep else _Ptr(None), _Ptr(C.addressof(sj)), _Ptr(C.addressof(bj)), bg.p[2]],
-                   tag="loss.bwd_fused", stream=lb.stream)
+                   tag="loss.bwd_fused")
         cmd.lane = getattr(lb, "lane", 0)
         cmd.members = [lb, bg] + list(sp.members)
         cmd.bias_jobs = bj
@@ -1085,41 +998,12 @@ class Plan:
         self.descs.append(d)
         return d
 
-    @staticmethod
-    def _lower_streams(cmds):
-        """stream-tagged commands inside par.begin / par.end markers -> FORK, STREAM switches, JOIN"""
-        out, k = [], 0
-        while k < len(cmds):
-            c = cmds[k]
-            if c.op == L.OP["NOP"] and c.tag.endswith(".begin"):
-                e = k + 1
-                while not (cmds[e].op == L.OP["NOP"] and cmds[e].tag.endswith(".end")):
-                    e += 1
-                region = cmds[k + 1: e]
-                used = sorted({r.stream for r in region if r.stream > 0})
-                out += [_Cmd(L.OP["FORK"], i=[sid], tag=f"fork{sid}") for sid in used]
-                # issue the auxiliary chains first (they are the short ones), the caller's stream last
-                for sid in used + [0]:
-                    chain = [r for r in region if r.stream == sid]
-                    if chain:
-                        out.append(_Cmd(L.OP["STREAM"], i=[sid], tag=f"stream{sid}"))
-                        out += chain
-                out += [_Cmd(L.OP["JOIN"], i=[sid], tag=f"join{sid}") for sid in used]
-                k = e + 1
-            else:
-                assert c.stream == 0, f"{c.tag}: stream {c.stream} outside a parallel region"
-                out.append(c)
-                k += 1
-        return out
-
     def _group_lanes(self, cmds):
         """parallel region = independent chains (lanes).  A list scheduler walks the chains in lock step: the op kind
         most lanes have next is issued for all of them at once - as ONE grouped launch when it is a convolution or a
         BatchNorm pass (CONV_GROUP / BN_GROUP), one command per lane otherwise.  Commands that write the same tensor
-        (two data gradients accumulating into one input gradient) are never grouped and keep their original order."""
-        b = self.b
-        if not b.group_lanes or b.multi_stream:
-            return cmds
+        (two data gradients accumulating into one input gradient) are never grouped and keep their original order.  The
+        region's .begin / .end NOP markers are dropped."""
         NOP, CONV = L.OP["NOP"], L.OP["CONV"]
         BN_KIND = {L.OP["BN_ACT_FWD"]: 0, L.OP["BN_BWD_REDUCE"]: 1, L.OP["BN_BWD_APPLY"]: 2, L.OP["BN_BWD_FUSED"]: 3}
 
@@ -1194,15 +1078,12 @@ class Plan:
             region = cmds[k + 1: e]
             order = {id(r): i for i, r in enumerate(region)}
             lanes = sorted({r.lane for r in region})
-            chains = [[r for r in region if r.lane == ln] for ln in lanes]
-            out.append(c)
             skip = os.environ.get("MI_GROUP_SKIP", "")
-            if len(lanes) < 2 or (skip and any(t and t in c.tag for t in skip.split(","))):
+            if not self.b.group_lanes or len(lanes) < 2 or (skip and any(t and t in c.tag for t in skip.split(","))):
                 out += region
             else:
                 for cs in schedule_lanes(region):
                     out += issue(cs, order)
-            out.append(cmds[e])
             k = e + 1
         return out
 
@@ -1216,7 +1097,7 @@ class Plan:
         while k < len(cmds):
             run = cmds[k:k + 4]
             base = cmds[k].tag[:-2] if cmds[k].op == CONV and cmds[k].tag.endswith(".dgrad00") else None
-            if base and len(run) == 4 and all(c.op == CONV and c.tag == base + s and c.lane == run[0].lane and c.stream == run[0].stream
+            if base and len(run) == 4 and all(c.op == CONV and c.tag == base + s and c.lane == run[0].lane
                                               for c, s in zip(run, ("00", "01", "10", "11"))):
                 g = self._conv_group_cmd(run[::-1], tag=base + "(4 classes)") or self._conv_group_cmd(run, tag=base + "(4 classes)")
                 if g is None and os.environ.get("MI_GROUP_PARITY_TPS1", "1") != "0":
@@ -1226,12 +1107,12 @@ class Plan:
                     for c in run[::-1]:
                         sp = ConvSpec(**c.desc.__dict__)
                         sp.tps = 1
-                        nc = _Cmd(c.op, c.i, c.f, c.p, c.l, sp, c.tag, stream=c.stream)
+                        nc = _Cmd(c.op, c.i, c.f, c.p, c.l, sp, c.tag)
                         nc.lane = c.lane
                         one.append(nc)
                     g = self._conv_group_cmd(one, tag=base + "(4 classes)")
                 if g is not None:
-                    g.lane, g.stream = run[0].lane, run[0].stream
+                    g.lane = run[0].lane
                     out.append(g)
                     k += 4
                     continue
@@ -1472,7 +1353,7 @@ class Plan:
                 sp.xf = _Ptr(tab, C.sizeof(L.mi_bnx) * [id(k_) for k_ in keys].index(id(bn)))
                 sp.xf_write, sp.xf_C = int(id(bn) not in seen), bn.i[3]
                 seen.add(id(bn))
-                nm = _Cmd(m.op, m.i, m.f, m.p, m.l, sp, m.tag, stream=m.stream)
+                nm = _Cmd(m.op, m.i, m.f, m.p, m.l, sp, m.tag)
                 nm.lane = m.lane
                 new.append(nm)
             if c.op == CONV:
@@ -1485,7 +1366,7 @@ class Plan:
                 res = self._conv_group_cmd(new, tag=c.tag)
                 if res is None:
                     return None
-                res.lane, res.stream = c.lane, c.stream
+                res.lane = c.lane
             self.descs.append(tab)
             res.deferred_bn = [ent[1] for _, ent in picks]
             return res, picks
@@ -1522,7 +1403,7 @@ class Plan:
                     if g is None:
                         out += rest
                     else:
-                        g.lane, g.stream = c.lane, c.stream
+                        g.lane = c.lane
                         out.append(g)
                 else:
                     out += rest
@@ -1540,7 +1421,7 @@ class Plan:
         j.eps, j.momentum = (c.f + [0.0, 0.0])[:2]
 
     def _materialize(self, cmds, which):
-        cmds = self._lower_streams(self._group_lanes(self._group_parity(cmds)))
+        cmds = self._group_lanes(self._group_parity(cmds))
         if which == "fwd":
             cmds = self._fuse_conv_bn(self._defer_bn(cmds))
         arr = (L.mi_cmd * max(1, len(cmds)))()
