@@ -6,7 +6,13 @@ gradient all-reduce + SGD update), bs=16/GPU, synthetic COCO-shaped data, on N M
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (see BASELINE.json for the metric).  `roofline` describes the dominant
+Rank 0 prints ONE JSON line (see BASELINE.json for the metric).  A plain run does only what that line's headline figure
+needs: set up, warm up, time the steps, write --dump-outputs, print.  Everything else is measured with
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+after the timed steps, each part in runs of its own.  Its line adds `roofline`, `value_incl_h2d`, `cpu_baseline` (and
+`ddp` with --gpus N).  `roofline` describes the dominant
 kernel class (the conv / wgrad class with the largest total time per step; since the head / CSP convs are grouped that is the grouped weight gradient), `cpu_baseline` the oracle
 (CPU fp32 restatement of the reference path) timed on this box's host cores on a bounded sample.
 
@@ -406,6 +412,32 @@ def roofline_block(plan, iters=5, live=None, trace=None, ms_per_step=None):
     return rl, breakdown, total_ms
 
 
+def yolox_roofline(args, st, ms, world):
+    """--full part of the YOLOX line: the per-class roofline of the step (live rocprofv3 counter passes and a kernel trace
+    of the replayed step, each in a child run of this file) -> (roofline block, per-class breakdown, kernel ms per step)"""
+    live = None
+    if world == 1 and os.environ.get("MI_BENCH_NO_PMC") != "1":      # (A/B scripts: tools/abn.sh skips the two counter passes)
+        # counters of THIS box (the committed CSV of an earlier box is only the fallback): the child must take the
+        # same BatchNorm backward form as this run
+        prev = os.environ.get("MI_BN_FUSED")
+        os.environ["MI_BN_FUSED"] = "1" if st["plan"].bn_fused else "0"
+        live = live_pmc_traffic(args)
+        if prev is None:
+            os.environ.pop("MI_BN_FUSED", None)
+        else:
+            os.environ["MI_BN_FUSED"] = prev
+    trace = live_kernel_trace(args) if (world == 1 and not args.no_graph and os.environ.get("MI_BENCH_NO_PMC") != "1") else None
+    rl, breakdown, kernel_ms = roofline_block(st["plan"], live=live, trace=trace, ms_per_step=ms)
+    if trace is not None and "in-graph" in rl["timing_source"]:
+        rl["whole_step"]["traced_step_span_ms"] = round(trace[1] * 1e-3, 3)
+        # the accounting must close: the dispatches of a step cannot add up to more than the step
+        closes = kernel_ms <= 1.02 * max(ms, trace[1] * 1e-3)
+        rl["whole_step"]["accounting_closes"] = bool(closes)
+        if os.environ.get("MI_BENCH_STRICT") == "1":
+            assert closes, (kernel_ms, ms, trace[1])
+    return rl, breakdown, kernel_ms
+
+
 def cpu_baseline(batch=16, size=640, steps=5):
     """CPU path timed on this box's host cores: fwd + SimOTA loss + bwd + SGD(momentum), fp32, the benchmark's batch.
     kind "reference": the reference's OWN modules loaded by path (oracle/ref_loader.py, only where /root/reference
@@ -589,10 +621,78 @@ def cpu_baseline_detr(model, inputs, nimg=2, steps=2):
                        "detr_oracle.py (CPU restatements; the reference tree is not on this box)")
 
 
+def detr_roofline(B, H_, W_, dev, ms_step):
+    """--full part of --config detr: the fused attention kernels alone at the encoder shape against the 2.5 PFLOP/s dense
+    bf16 peak, with and without attention dropout, and the whole step's algorithmic flops over `ms_step`"""
+    # attention kernels alone, encoder self-attention shape: 20 back-to-back launches through the C-ABI between HIP events
+    # on the launch stream (the autograd wrapper's Python time - ~35 us per call - is not the kernel's)
+    from yolov7_d2_amd import _lib as L
+    L_, E, nh = (H_ // 32) * ((W_ + 31) // 32), 256, 8
+    q, k, v, go = (torch.randn(L_, B, E, device=dev).to(torch.bfloat16) for _ in range(4))
+    o, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
+    lse, dws = (torch.empty(B, nh, L_, device=dev) for _ in range(2))
+    lib, spx, scl = L.lib(), L.stream_ptr(), 1.0 / 32 ** 0.5
+    fwd = lambda: L.check(lib.mi_mha_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), B, nh, L_, L_, E, scl, spx), "mha_fwd")
+    bwd = lambda: L.check(lib.mi_mha_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), go.data_ptr(), dws.data_ptr(),
+                                         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, nh, L_, L_, E, scl, spx), "mha_bwd")
+    times = []
+    for fn in (fwd, bwd):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) / 20)
+    tf, tb = times
+    # the same forward as the step runs it: attention-weight dropout p = 0.1 (counter-based mask recomputed in the backward)
+    fwd_d = lambda: L.check(lib.mi_mha_fwd_dropout(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), B, nh, L_, L_, E,
+                                                   scl, 0.1, 12345, spx), "mha_fwd_dropout")
+    bwd_d = lambda: L.check(lib.mi_mha_bwd_dropout(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), go.data_ptr(),
+                                                   dws.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, nh, L_, L_, E, scl, 0.1, 12345, spx),
+                            "mha_bwd_dropout")
+    times_d = []
+    for fn in (fwd_d, bwd_d):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        times_d.append(e0.elapsed_time(e1) / 20)
+    tfd, tbd = times_d
+    fl_f = 4.0 * L_ * L_ * 32 * B * nh
+    fl_b = 2.5 * fl_f          # dP, dV, dS->dQ, dK + the recomputed scores (x2: dq and dkv kernels each recompute S)
+    Hp, Wp = (H_ + 63) // 64 * 64, (W_ + 63) // 64 * 64      # Detr.shape_bucket = 64: the padded tensor the step computes on
+    alg, alg_parts = detr_algorithmic_flops(B, Hp, Wp)
+    return {"bound": "mfma", "kernel": "mha_fwd2_kernel WITH attention dropout p=0.1, as the step runs it (encoder self-attention, L=%d, B=%d, 8 heads x 32)" % (L_, B),
+            "achieved": round(fl_f / (tfd * 1e-3) / 1e12, 1), "peak": 2500.0, "unit": "TFLOP/s",
+            "frac": round(fl_f / (tfd * 1e-3) / 1e12 / 2500.0, 4), "traffic": None, "avg_launch_ms": round(tfd, 4),
+            "without_dropout": {"achieved": round(fl_f / (tf * 1e-3) / 1e12, 1), "frac": round(fl_f / (tf * 1e-3) / 1e12 / 2500.0, 4),
+                                "avg_launch_ms": round(tf, 4)},
+            "mha_bwd_with_dropout": {"achieved": round(fl_b / (tbd * 1e-3) / 1e12, 1), "unit": "TFLOP/s",
+                                     "frac": round(fl_b / (tbd * 1e-3) / 1e12 / 2500.0, 4), "ms": round(tbd, 4)},
+            "mha_bwd": {"achieved": round(fl_b / (tb * 1e-3) / 1e12, 1), "unit": "TFLOP/s",
+                        "frac": round(fl_b / (tb * 1e-3) / 1e12 / 2500.0, 4), "ms": round(tb, 4),
+                        "kernels": "mha_delta + mha_bwd_dq2 + mha_bwd_dkv2"},
+            "whole_step": {"algorithmic_flops": alg, "parts_GFLOP": {k_: round(v_ / 1e9, 1) for k_, v_ in alg_parts.items()},
+                           "padded_batch": [B, 3, Hp, Wp], "ms_per_step": round(ms_step, 3),
+                           "mfma_tflops": round(alg / (ms_step * 1e-3) / 1e12, 1),
+                           "mfma_frac_of_2500": round(alg / (ms_step * 1e-3) / 1e12 / 2500.0, 4),
+                           "note": "2 flops per multiply-add; fwd + dgrad + wgrad of the trainable layers, forward only for the "
+                                   "frozen stem + res2, attention backward 2.5 x forward (bench.detr_algorithmic_flops)"}}
+
+
 def bench_detr(args):
     """--config detr: BASELINE.json configs[3] - DETR-R50 (6 + 6 layers, 100 queries, dropout 0.1) training step at
     800 x 1333 (the padded batch of the reference's MIN_SIZE_TRAIN 800 / MAX 1333), fwd + Hungarian matching + set
-    criterion + bwd + AdamW, plus the MFMA utilisation of the fused attention kernels at the encoder shape
+    criterion + bwd + AdamW; with --full also the MFMA utilisation of the fused attention kernels at the encoder shape
     (L = 25 x 42 = 1050 tokens) against the 2.5 PFLOP/s dense bf16 peak."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import yolov7_d2_amd as M
@@ -652,7 +752,7 @@ def bench_detr(args):
                                              params_sample=seeded_sample(torch.cat([p.detach().reshape(-1) for p in params]), 1 << 22, seed=1)))
     # the reference's own per-GPU batch: IMS_PER_BATCH 56 on 8 GPUs = 7 (configs/coco/detr/detr_256_6_6_torchvision.yaml:26)
     bs7 = None
-    if graphed and args.batch == 16 and os.environ.get("MI_BENCH_DETR_BS7", "1") == "1":
+    if args.full and graphed and args.batch == 16 and os.environ.get("MI_BENCH_DETR_BS7", "1") == "1":
         g7 = torch.Generator().manual_seed(4321)
         in7 = list(inputs)
         for b in range(B, 7):
@@ -672,53 +772,6 @@ def bench_detr(args):
         d7 = time.perf_counter() - t1
         bs7 = dict(batch=7, value=round(7 * args.steps / d7, 2), ms_per_step=round(d7 / args.steps * 1e3, 3),
                    note="the reference's per-GPU batch (IMS_PER_BATCH 56 / 8 GPUs)")
-    # attention kernels alone, encoder self-attention shape: 20 back-to-back launches through the C-ABI between HIP events
-    # on the launch stream (the autograd wrapper's Python time - ~35 us per call - is not the kernel's)
-    from yolov7_d2_amd import _lib as L
-    L_, E, nh = (H_ // 32) * ((W_ + 31) // 32), 256, 8
-    q, k, v, go = (torch.randn(L_, B, E, device=dev).to(torch.bfloat16) for _ in range(4))
-    o, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
-    lse, dws = (torch.empty(B, nh, L_, device=dev) for _ in range(2))
-    lib, spx, scl = L.lib(), L.stream_ptr(), 1.0 / 32 ** 0.5
-    fwd = lambda: L.check(lib.mi_mha_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), B, nh, L_, L_, E, scl, spx), "mha_fwd")
-    bwd = lambda: L.check(lib.mi_mha_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), go.data_ptr(), dws.data_ptr(),
-                                         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, nh, L_, L_, E, scl, spx), "mha_bwd")
-    times = []
-    for fn in (fwd, bwd):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1) / 20)
-    tf, tb = times
-    # the same forward as the step runs it: attention-weight dropout p = 0.1 (counter-based mask recomputed in the backward)
-    fwd_d = lambda: L.check(lib.mi_mha_fwd_dropout(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), B, nh, L_, L_, E,
-                                                   scl, 0.1, 12345, spx), "mha_fwd_dropout")
-    bwd_d = lambda: L.check(lib.mi_mha_bwd_dropout(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, o.data_ptr(), lse.data_ptr(), go.data_ptr(),
-                                                   dws.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, nh, L_, L_, E, scl, 0.1, 12345, spx),
-                            "mha_bwd_dropout")
-    times_d = []
-    for fn in (fwd_d, bwd_d):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        times_d.append(e0.elapsed_time(e1) / 20)
-    tfd, tbd = times_d
-    fl_f = 4.0 * L_ * L_ * 32 * B * nh
-    fl_b = 2.5 * fl_f          # dP, dV, dS->dQ, dK + the recomputed scores (x2: dq and dkv kernels each recompute S)
-    Hp, Wp = (H_ + 63) // 64 * 64, (W_ + 63) // 64 * 64      # Detr.shape_bucket = 64: the padded tensor the step computes on
-    alg, alg_parts = detr_algorithmic_flops(B, Hp, Wp)
     ms_step = dt / args.steps * 1e3
     out = {
         "metric": "images/sec training, DETR-R50 800x1333", "value": round(B * args.steps / dt, 2), "unit": "images/sec",
@@ -729,27 +782,13 @@ def bench_detr(args):
                                + ("(one hipGraph per padded shape, host half outside)" if graphed else "(eager ops)"),
                    "hipgraph": graphed,
                    "final_loss": round(float(last), 4)},
-        "roofline": {"bound": "mfma", "kernel": "mha_fwd2_kernel WITH attention dropout p=0.1, as the step runs it (encoder self-attention, L=%d, B=%d, 8 heads x 32)" % (L_, B),
-                     "achieved": round(fl_f / (tfd * 1e-3) / 1e12, 1), "peak": 2500.0, "unit": "TFLOP/s",
-                     "frac": round(fl_f / (tfd * 1e-3) / 1e12 / 2500.0, 4), "traffic": None, "avg_launch_ms": round(tfd, 4),
-                     "without_dropout": {"achieved": round(fl_f / (tf * 1e-3) / 1e12, 1), "frac": round(fl_f / (tf * 1e-3) / 1e12 / 2500.0, 4),
-                                         "avg_launch_ms": round(tf, 4)},
-                     "mha_bwd_with_dropout": {"achieved": round(fl_b / (tbd * 1e-3) / 1e12, 1), "unit": "TFLOP/s",
-                                              "frac": round(fl_b / (tbd * 1e-3) / 1e12 / 2500.0, 4), "ms": round(tbd, 4)},
-                     "mha_bwd": {"achieved": round(fl_b / (tb * 1e-3) / 1e12, 1), "unit": "TFLOP/s",
-                                 "frac": round(fl_b / (tb * 1e-3) / 1e12 / 2500.0, 4), "ms": round(tb, 4),
-                                 "kernels": "mha_delta + mha_bwd_dq2 + mha_bwd_dkv2"},
-                     "whole_step": {"algorithmic_flops": alg, "parts_GFLOP": {k_: round(v_ / 1e9, 1) for k_, v_ in alg_parts.items()},
-                                    "padded_batch": [B, 3, Hp, Wp], "ms_per_step": round(ms_step, 3),
-                                    "mfma_tflops": round(alg / (ms_step * 1e-3) / 1e12, 1),
-                                    "mfma_frac_of_2500": round(alg / (ms_step * 1e-3) / 1e12 / 2500.0, 4),
-                                    "note": "2 flops per multiply-add; fwd + dgrad + wgrad of the trainable layers, forward only for the "
-                                            "frozen stem + res2, attention backward 2.5 x forward (bench.detr_algorithmic_flops)"}},
     }
-    if bs7 is not None:
-        out["at_reference_batch"] = bs7
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline_detr(model, inputs)
+    if args.full:
+        out["roofline"] = detr_roofline(B, H_, W_, dev, ms_step)
+        if bs7 is not None:
+            out["at_reference_batch"] = bs7
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline_detr(model, inputs)
     print(json.dumps(out))
 
 
@@ -788,7 +827,7 @@ def _time_conv(K, Cout, N, H, W, taps, iters=20):
 def bench_sparseinst(args):
     """--config sparseinst: BASELINE.json configs[4] on ONE GPU - SparseInst-R50 (InstanceContextEncoder + GroupIAMDecoder,
     100 instance queries, FREEZE_AT 0) training step at 640 x 640: fwd + matcher + criterion (focal / dice / BCE / objectness)
-    + bwd + AdamW on bitmask targets.  roofline = the decoder's 3x3 256-channel convolution stack at 80 x 80 (eight such
+    + bwd + AdamW on bitmask targets.  --full adds roofline = the decoder's 3x3 256-channel convolution stack at 80 x 80 (eight such
     layers per step: 4 instance-branch + 4 mask-branch) on the matrix cores."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import yolov7_d2_amd as M
@@ -843,8 +882,6 @@ def bench_sparseinst(args):
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, dict(total_loss=last.reshape(1),
                                              params_sample=seeded_sample(torch.cat([p.detach().reshape(-1) for p in params]), 1 << 22, seed=1)))
-    ms, fl, byt = _time_conv(256, 256, B, S // 8, S // 8, 9)
-    tf = fl / (ms * 1e-3) / 1e12
     out = {
         "metric": "images/sec training, SparseInst-R50 640x640", "value": round(B * args.steps / dt, 2), "unit": "images/sec",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -852,12 +889,15 @@ def bench_sparseinst(args):
         "config": {"workload": f"SparseInst-R50 G-IAM (100 queries, FREEZE_AT 0) bs={B}/GPU {S}x{S}: fwd + matcher + criterion + "
                                "bwd + AdamW, random rectangle / ellipse bitmask targets",
                    "hipgraph": graphed, "final_loss": round(float(last), 4)},
-        "roofline": {"bound": "mfma", "kernel": f"conv_igemm_kernel, 3x3 256->256 at {S // 8}x{S // 8}, B={B} (the decoder's eight-layer stack)",
-                     "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4), "traffic": None,
-                     "avg_launch_ms": round(ms, 4), "algorithmic_flops_per_launch": int(fl), "algorithmic_bytes_per_launch": int(byt)},
     }
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline_sparseinst(S)
+    if args.full:
+        ms, fl, byt = _time_conv(256, 256, B, S // 8, S // 8, 9)
+        tf = fl / (ms * 1e-3) / 1e12
+        out["roofline"] = {"bound": "mfma", "kernel": f"conv_igemm_kernel, 3x3 256->256 at {S // 8}x{S // 8}, B={B} (the decoder's eight-layer stack)",
+                           "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4), "traffic": None,
+                           "avg_launch_ms": round(ms, 4), "algorithmic_flops_per_launch": int(fl), "algorithmic_bytes_per_launch": int(byt)}
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline_sparseinst(S)
     print(json.dumps(out))
 
 
@@ -973,20 +1013,27 @@ def main():
               would be a second implementation behind the same API, which the scope contract rules out).  The tiny network
               itself is covered on the HIP device against a golden of the reference's own modules
               (tests/test_gpu_widths.py, tests/golden/yolox_tiny_step_416.npz); the reference CPU path timed beside the
-              GPU number is the `cpu_baseline` block of the line below.
+              GPU number is the `cpu_baseline` block of the --full line.
   configs[1]  this program's default line (N = 1).      configs[2]  --gpus 8 (one rank per GPU, RCCL).
   configs[3]  --config detr (builder-run; not the driver's metric).      configs[4]  --config sparseinst (one GPU).
 `value` keeps the uint8 batch resident in HBM when the timed region starts (the task contract); SURVEY.md 8(d) defines the
-step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed from pinned memory, double-buffered).""")
+step WITH the host -> device copy of the batch: that is `value_incl_h2d` (--full; fed from pinned memory, double-buffered).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line (value, ms_per_step, config with
+the final losses).  --full adds every other measurement, each in runs of its own after the timed steps: `roofline` (live
+rocprofv3 counter and trace passes), `value_incl_h2d`, `cpu_baseline`, the `ddp` block of --gpus N; for --config detr /
+sparseinst their `roofline` and `cpu_baseline`, and detr's `at_reference_batch` line.""")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-fed (PCIe-inclusive) measurement")
-    ap.add_argument("--breakdown", type=str, default="", help="write the per-kernel-class breakdown JSON here")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything besides the headline figure: roofline, value_incl_h2d, "
+                         "cpu_baseline, ddp (--gpus N), the secondary configs' rooflines, CPU baselines and batch-7 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-h2d", action="store_true", help="(--full) skip the host-fed (PCIe-inclusive) measurement")
+    ap.add_argument("--breakdown", type=str, default="", help="(--full) write the per-kernel-class breakdown JSON here")
     ap.add_argument("--config", type=str, default="yolox", help="yolox (the headline metric) | detr (BASELINE configs[3]) | sparseinst (configs[4], one GPU)")
     ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
                     help="write what the last timed step computed as DIR/<name>.npy (float32, 64 MB at most in all): "
@@ -995,6 +1042,8 @@ step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed fr
     ap.add_argument("--pmc-child", action="store_true", help="(internal) a few eager steps under rocprofv3 --pmc, no output")
     ap.add_argument("--trace-child", action="store_true", help="(internal) graph-replayed steps under rocprofv3 --kernel-trace, no output")
     args = ap.parse_args()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown comes from the roofline measurement: it needs --full")
     if args.pmc_child:
         return pmc_child(args)
     if args.trace_child:
@@ -1065,7 +1114,7 @@ step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed fr
     value = args.batch * world * args.steps / dt
 
     ddp = None
-    if world > 1:
+    if args.full and world > 1:
         # self-explaining scaling line: the buckets, what each all-reduce costs alone, and how much of the communication
         # is NOT hidden under backward (same timed loop with the collectives skipped)
         red = st["red"]
@@ -1100,29 +1149,9 @@ step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed fr
                    bwd_segments=len(st["segs"]), ms_per_step_without_allreduce=round(float(t_nocomm) / args.steps * 1e3, 3),
                    exposed_comm_ms=round(ms - float(t_nocomm) / args.steps * 1e3, 3))
     incl = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         incl = h2d_inclusive(model, args, world, rank, dev)
     if rank == 0:
-        live = None
-        if world == 1 and os.environ.get("MI_BENCH_NO_PMC") != "1":      # (A/B scripts: tools/abn.sh skips the two counter passes)
-            # counters of THIS box (the committed CSV of an earlier box is only the fallback): the child must take the
-            # same BatchNorm backward form as this run
-            prev = os.environ.get("MI_BN_FUSED")
-            os.environ["MI_BN_FUSED"] = "1" if st["plan"].bn_fused else "0"
-            live = live_pmc_traffic(args)
-            if prev is None:
-                os.environ.pop("MI_BN_FUSED", None)
-            else:
-                os.environ["MI_BN_FUSED"] = prev
-        trace = live_kernel_trace(args) if (world == 1 and not args.no_graph and os.environ.get("MI_BENCH_NO_PMC") != "1") else None
-        rl, breakdown, kernel_ms = roofline_block(st["plan"], live=live, trace=trace, ms_per_step=ms)
-        if trace is not None and "in-graph" in rl["timing_source"]:
-            rl["whole_step"]["traced_step_span_ms"] = round(trace[1] * 1e-3, 3)
-            # the accounting must close: the dispatches of a step cannot add up to more than the step
-            closes = kernel_ms <= 1.02 * max(ms, trace[1] * 1e-3)
-            rl["whole_step"]["accounting_closes"] = bool(closes)
-            if os.environ.get("MI_BENCH_STRICT") == "1":
-                assert closes, (kernel_ms, ms, trace[1])
         out = {
             "metric": "images/sec training, YOLOX-s 640x640 bs=16/GPU", "value": round(value, 2),
             "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1131,32 +1160,35 @@ step WITH the host -> device copy of the batch: that is `value_incl_h2d` (fed fr
             "config": {"workload": f"YOLOX-s CSPDarknet+PAFPN {args.size}x{args.size} bs={args.batch}/GPU: fwd + SimOTA "
                                    "loss + bwd + grad all-reduce + SGD(momentum) step, uint8 image batch + labels resident in HBM",
                        "value_definition": "inputs resident in HBM at the start of the timed region (task contract); SURVEY 8(d)'s "
-                                           "step includes the host->device copy of each batch: value_incl_h2d",
+                                           "step includes the host->device copy of each batch: value_incl_h2d (--full)",
                        "global_batch": args.batch * world, "parallelism": f"dp{world}",
-                       "hipgraph": not args.no_graph, "sum_kernel_ms_per_step": round(kernel_ms, 3),
+                       "hipgraph": not args.no_graph,
                        "final_losses": [round(x, 4) for x in losses],
                        "bn_backward": dict(form="fused (one launch, grid barrier)" if st["plan"].bn_fused else "reduce + apply",
                                            selected_on_device=st["plan"].bn_fused_timing)},
-            "roofline": rl,
         }
-        if ddp is not None:
-            out["ddp"] = ddp
-        if incl is not None:
-            # the same step fed from pinned host memory (fresh uint8 batch per step, double-buffered, overlapped):
-            # SURVEY 8(d)'s definition of the step; `value` keeps the inputs resident as the task statement prescribes
-            out["value_incl_h2d"] = round(incl[0], 2)
-            out["ms_per_step_incl_h2d"] = round(incl[1], 3)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
-            # the box this runs on has no /root/reference, so the live leg above can only be the restatement ("port"); the
-            # REFERENCE'S OWN modules timed where that tree exists (the build container, 8 cores) are recorded under profiles/
-            rec = os.path.join(ROOT, "profiles", "r04_cpu_baseline_reference.json")
-            if out["cpu_baseline"]["kind"] != "reference" and os.path.exists(rec):
-                with open(rec) as f:
-                    out["cpu_baseline"]["reference_recorded"] = json.load(f)
-        if args.breakdown:
-            with open(args.breakdown, "w") as f:
-                json.dump(breakdown, f, indent=1)
+        if args.full:
+            rl, breakdown, kernel_ms = yolox_roofline(args, st, ms, world)
+            out["config"]["sum_kernel_ms_per_step"] = round(kernel_ms, 3)
+            out["roofline"] = rl
+            if ddp is not None:
+                out["ddp"] = ddp
+            if incl is not None:
+                # the same step fed from pinned host memory (fresh uint8 batch per step, double-buffered, overlapped):
+                # SURVEY 8(d)'s definition of the step; `value` keeps the inputs resident as the task statement prescribes
+                out["value_incl_h2d"] = round(incl[0], 2)
+                out["ms_per_step_incl_h2d"] = round(incl[1], 3)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline()
+                # where the reference tree is absent the live leg above can only be the restatement ("port"); the
+                # REFERENCE'S OWN modules timed where that tree exists (the build container, 8 cores) are recorded under profiles/
+                rec = os.path.join(ROOT, "profiles", "r04_cpu_baseline_reference.json")
+                if out["cpu_baseline"]["kind"] != "reference" and os.path.exists(rec):
+                    with open(rec) as f:
+                        out["cpu_baseline"]["reference_recorded"] = json.load(f)
+            if args.breakdown:
+                with open(args.breakdown, "w") as f:
+                    json.dump(breakdown, f, indent=1)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -74,7 +74,7 @@ def test_bench_starts_itself_for_n_gpus():
     # (a small batch: two ranks share one device here and the gradient exchange goes through gloo's host staging - the
     # schedule selection alone runs ~20 backward passes with their all-reduces)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--batch", "4", "--size", "320", "--no-cpu-baseline", "--no-h2d"], env=env, stdout=subprocess.PIPE,
+                        "--batch", "4", "--size", "320", "--full", "--no-cpu-baseline", "--no-h2d"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
