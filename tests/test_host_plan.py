@@ -551,3 +551,176 @@ def test_wgrad_fixup_table_layout(monkeypatch):
         k = by_g[4096 * (i + 1)]
         assert (k.Cout, k.Cin, k.accumulate) == (d.Cout, d.Cin, d.accumulate)
         assert k.nsplit * k.V * 16 < 2 ** 31                                      # the fix-up's 32-bit slab offsets
+
+
+@pytest.mark.parametrize("env", [{}, {"MI_GROUP_LEVELS": "0"}, {"MI_WGRAD_SPLIT": "1"}, {"MI_BN_IN_CONSUMER": "1"},
+                                 {"MI_FUSE_BN_BWD": "1"}, {"MI_BN_FUSED": "0"}, {"MI_BN_FUSED": "1"}],
+                         ids=["default", "levels0", "wgrad_split", "bn_in_consumer", "fuse_bn_bwd", "bn_fused0", "bn_fused1"])
+def test_materialized_lists_mean_the_builder_lists(monkeypatch, env):
+    """the MATERIALISED command lists (lane scheduling, parity groups, BatchNorm in the consumer, fused BatchNorm backward
+    pairs, batched prediction splits, the fused loss backward, the staged weight-gradient groups, the weight-pack batch)
+    interpreted through their members - Plan.cmd_objs / cmd_members - compute what the builder's lists compute: losses,
+    every parameter gradient and the BatchNorm running statistics to fp32 reordering noise.  A reader scheduled before its
+    writer, a dropped or doubled member or a lost accumulation shows up as an O(1) error."""
+    from yolov7_d2_amd.plan import Plan
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    model, _ = _model(seed=4)
+    B, H, W = 2, 64, 96
+    imgs, labels = O.synth_batch(B, H, W, seed=13, max_gt=4)
+    ps = _PlanState(model, B, H, W, True, materialize=False)
+    b = ps.builder
+    plan = Plan(b, dry_run=True)
+    if env.get("MI_BN_IN_CONSUMER") == "1":
+        assert len(plan.deferred_bn) >= 20      # (26 at this size; the streaming kernels do not take every small map)
+    ps.image.copy_(imgs)
+    ps.labels.copy_(labels)
+    state0 = [(t, t.clone()) for t in b.tune_restore]
+    res = {}
+    for form in ("builder", "materialized"):
+        for t, v in state0:
+            t.copy_(v)
+        model.params.grad.zero_()
+        it = Interp(b, torch.float32)
+        if form == "builder":
+            it.run(b.prologue + b.fwd)
+        else:
+            it.run_materialized(plan, "fwd")
+        out = it.raw(ps.loss["out"]).view(torch.float32)[:8].clone()
+        it.raw(ps.loss["gw"]).view(torch.float32)[:4] = 1.0
+        if form == "builder":
+            it.run(b.bwd)
+        else:
+            it.run_materialized(plan, "bwd")
+        res[form] = (out, model.params.grad.clone(), [t.clone() for t, _ in state0])
+    (o0, g0, s0), (o1, g1, s1) = res["builder"], res["materialized"]
+    np.testing.assert_allclose(o1.numpy(), o0.numpy(), rtol=1e-5, atol=1e-7)
+    assert float(o0[6]) > 0
+    bad = []
+    for name, p, off, cnt in model.params.entries:
+        a, r = g1[off: off + cnt], g0[off: off + cnt]
+        rel = float((a - r).norm() / (r.norm() + 1e-30))
+        if rel > 1e-5:           # (a gradient that is zero - a head level without foreground - must stay zero)
+            bad.append((name, rel))
+    assert not bad, bad[:8]
+    assert sum(float(g0[off: off + cnt].norm()) > 0 for _, _, off, cnt in model.params.entries) > 0.9 * len(model.params.entries)
+    for a, r in zip(s1, s0):
+        if r.is_floating_point():
+            assert float((a - r).norm() / (r.norm() + 1e-30)) <= 1e-5
+        else:
+            assert torch.equal(a, r)
+
+
+def test_materialized_lists_cover_every_builder_command():
+    """every symbolic command of the builder's lists is a member of exactly one materialised command (the weight packs of
+    PACK_W_BATCH and the layers of a WGRAD_GROUP included); the region markers are the only ones dropped"""
+    from yolov7_d2_amd.plan import Plan
+    model, _ = _model()
+    ps = _PlanState(model, 2, 64, 96, True, materialize=False)
+    b = ps.builder
+    plan = Plan(b, dry_run=True)
+    for which, sym in (("fwd", b.prologue + b.fwd), ("bwd", b.bwd)):
+        ran = [m for c in plan.cmd_objs[which] for m in Interp.members(c)]
+        assert len(ran) == len({id(m) for m in ran})
+        want = {id(c) for c in sym if not (L.OPS[c.op] == "NOP" and c.tag.endswith((".begin", ".end")))}
+        got = {id(m) for m in ran if not getattr(m.desc, "xf", None)}
+        # (a convolution that applies its input's BatchNorm is a copy of its builder command; its BN_ACT_FWD is absorbed)
+        xf = [m for m in ran if getattr(m.desc, "xf", None) is not None]
+        absorbed = {id(m.desc.xf_bn) for m in xf}
+        assert got | absorbed | {id(c) for c in sym if any(c.tag == m.tag and c.op == m.op for m in xf)} == want
+    ops = [L.OPS[c.op] for c in plan.cmd_objs["fwd"]]
+    k = ops.index("PACK_W_BATCH")
+    assert len(plan.cmd_members["fwd"][k]) == sum(c.op == L.OP["PACK_W"] for c in b.prologue)
+    k = [L.OPS[c.op] for c in plan.cmd_objs["bwd"]].index("WGRAD_GROUP")
+    assert len(plan.cmd_members["bwd"][k]) == sum(c.op == L.OP["WGRAD"] for c in b.bwd)
+
+
+def _synthetic_case(seed=0):
+    """a 2 x 24 x 40 image of a 64-channel concat buffer whose channel slice [16, 48) is the command's output view and
+    [48, 64) a view it only reads, and a plausible correct device result: the reference rounded differently by up to one
+    bf16 ulp on a few percent of the output's elements"""
+    from plan_compare import Layout
+    from yolov7_d2_amd.plan import Buf, TRef, _Cmd, _Ptr
+    N, H, W, ld = 2, 24, 40, 64
+    buf = Buf("neck.cat", N * H * W * ld * 2)
+    t = TRef(buf, N, H, W, 32, ld, 16)
+    g = torch.Generator().manual_seed(seed)
+    ref = torch.randn(N, H, W, ld, generator=g).to(torch.bfloat16)
+    got = ref.clone()
+    flip = torch.rand(N, H, W, ld, generator=g) < 0.05
+    sub = got[..., 16:48].view(torch.int16)
+    sub += (flip[..., 16:48] & (torch.rand(N, H, W, 32, generator=g) < 0.5)).to(torch.int16)   # +1 ulp (same sign)
+    got[..., 16:48] = sub.view(torch.bfloat16)
+    cmd = _Cmd(L.OP["UPSAMPLE_BWD"], p=[_Ptr(TRef(buf, N, H, W, 16, ld, 48)), _Ptr(t)])
+    return buf, Layout([cmd]), got, ref
+
+
+def test_comparator_passes_rounding_noise_and_flags_subtle_damage():
+    """tests/plan_compare.py on synthetic bf16 tensors: one-ulp rounding differences pass; a 16 x 16 tile off by 4 ulps,
+    one dropped pixel row, one channel scaled by 1.005 (< 1.3 ulps per element) and one byte changed in a sibling concat
+    slice the command only reads (or does not name at all) are each flagged, with the buffer and the first bad
+    (n, h, w, c)"""
+    from plan_compare import Report, compare_buffer
+
+    def run(got):
+        rep = Report()
+        ok = compare_buffer(buf, got.view(-1).view(torch.uint8), ref.view(-1).view(torch.uint8), lay, rep, tag="t", op="CONV")
+        return ok, rep
+
+    buf, lay, got, ref = _synthetic_case()
+    ok, rep = run(got)
+    assert ok, str(rep)
+    # (1) a 16 x 16 pixel tile of one channel group off by 4 ulps
+    bad = got.clone()
+    v = bad[1, 4:20, 8:24, 24:32].view(torch.int16)
+    v += 4
+    ok, rep = run(bad)
+    assert not ok and rep.fails[0]["kind"] == "bf16" and rep.fails[0]["first"][:3] == (1, 4, 8), str(rep)
+    # (2) a dropped pixel row (stale zeros)
+    bad = got.clone()
+    bad[0, 7, :, 16:48] = 0
+    ok, rep = run(bad)
+    assert not ok and rep.fails[0]["first"][:2] == (0, 7), str(rep)
+    # (3) one channel scaled by 1.005
+    bad = got.clone()
+    bad[..., 37] = (bad[..., 37].float() * 1.005).to(torch.bfloat16)
+    ok, rep = run(bad)
+    assert not ok and any(f["kind"] == "bf16-gain" and f["first"] == ("channel", 37) for f in rep.fails), str(rep)
+    assert not any(f["kind"] == "bf16" for f in rep.fails)       # (no element is off by more than the ulp bound)
+    # (4) one byte of a sibling slice the command reads (channel 50: a one-ulp stray store), (5) of one it does not name
+    for ch in (50, 5):
+        bad = got.clone()
+        bb = bad.view(-1).view(torch.uint8)
+        i = ((1 * 24 + 3) * 40 + 5) * 64 * 2 + ch * 2
+        bb[i] ^= 1
+        ok, rep = run(bad)
+        assert not ok and rep.fails[0]["kind"] == "exact" and rep.fails[0]["first"] == (1, 3, 5, ch), str(rep)
+
+
+def test_comparator_fp32_and_accumulator_rules():
+    """fp32 reductions: reordering noise passes, a 3e-5 error (of max|ref|) on one element fails; fp64 slot accumulators are compared
+    as sums over their slots (the device spreads a channel over slots, the interpreter adds to slot 0)"""
+    from plan_compare import Layout, Report, compare_buffer
+    from yolov7_d2_amd.plan import Buf, _Cmd, _Ptr, TRef
+    g = torch.Generator().manual_seed(1)
+    sc = Buf("backbone.stem.conv.scale", 64 * 4)
+    r = torch.randn(64, generator=g)
+    noisy = r * (1 + 1e-7 * torch.randn(64, generator=g))
+    lay = Layout([])
+    rep = Report()
+    assert compare_buffer(sc, noisy.view(torch.uint8), r.view(torch.uint8), lay, rep)
+    bad = noisy.clone()
+    bad[5] += 3e-5 * float(r.abs().max())
+    assert not compare_buffer(sc, bad.view(torch.uint8), r.view(torch.uint8), lay, rep) and rep.fails[-1]["first"] == 5
+    # accumulators: 4 slots x 32 channels x (sum, sumsq)
+    acc = Buf("scratch.bn_acc_fwd", 4 * 32 * 16)
+    y = TRef(Buf("y", 64), 1, 1, 1, 32, 32)
+    cmd = _Cmd(L.OP["BN_ACT_FWD"], i=[32, 0, 32, 32, 1, 4], p=[_Ptr(y), _Ptr(acc, 0)] + [_Ptr(None)] * 11, l=[1, 1])
+    lay = Layout([cmd])
+    dev = torch.randn(4, 32, 2, dtype=torch.float64, generator=g)
+    ref = torch.zeros_like(dev)
+    ref[0] = dev.sum(0)
+    rep = Report()
+    assert compare_buffer(acc, dev.view(-1).view(torch.uint8), ref.view(-1).view(torch.uint8), lay, rep), str(rep)
+    dev[2, 7, 0] += 0.5
+    assert not compare_buffer(acc, dev.view(-1).view(torch.uint8), ref.view(-1).view(torch.uint8), lay, rep)

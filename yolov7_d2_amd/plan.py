@@ -787,7 +787,7 @@ class Plan:
             self._materialize_bwd()
             arr, n = self.bwd_cmds
             keep[fused] = (self.bwd_cmds, self.bwd_tags, self.cmd_descs["bwd"], self.cmd_members["bwd"],
-                           list(self.wgrad_descs), list(getattr(self, "wgrad_stage_tags", [])))
+                           list(self.wgrad_descs), list(getattr(self, "wgrad_stage_tags", [])), self.cmd_objs["bwd"])
             with torch.cuda.stream(s):
                 L.check(lib.mi_cmdlist_run(arr, n, sp), "bn select: eager run")
                 handles[fused] = L.check(lib.mi_graph_capture(arr, n, sp), "bn select: capture")
@@ -808,7 +808,7 @@ class Plan:
         self.bn_fused_timing = dict(fused_ms=round(best[True], 4), two_pass_ms=round(best[False], 4))
         self.bn_fused = best[True] <= best[False]
         (self.bwd_cmds, self.bwd_tags, self.cmd_descs["bwd"], self.cmd_members["bwd"], self.wgrad_descs,
-         self.wgrad_stage_tags) = keep[self.bn_fused]
+         self.wgrad_stage_tags, self.cmd_objs["bwd"]) = keep[self.bn_fused]
 
     def _group_wgrads(self, bwd):
         """all WGRAD commands become ONE grouped launch at the end of backward (mi_conv2d_wgrad_group_run) - or two when
@@ -867,6 +867,7 @@ class Plan:
         self.wgrad_descs += list(descs)
         grp = _Cmd(L.OP["WGRAD_GROUP"], p=[_Ptr(C.addressof(meta)), _Ptr(table)], tag=tag)
         grp.group_descs = list(descs)
+        grp.parts = list(wg)
         return grp
 
     def _fuse_bn_bwd_pairs(self, bwd):
@@ -952,7 +953,9 @@ class Plan:
         nblk = L.check(L.lib().mi_pack_jobs_layout(jobs, len(packs)), "pack_jobs_layout")
         tab = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(self.b.device)
         self.pack_table = tab
-        return rest + [_Cmd(L.OP["PACK_W_BATCH"], i=[len(packs), nblk, max(j.KK for j in jobs)], p=[_Ptr(tab)], tag="pack_all")]
+        cmd = _Cmd(L.OP["PACK_W_BATCH"], i=[len(packs), nblk, max(j.KK for j in jobs)], p=[_Ptr(tab)], tag="pack_all")
+        cmd.parts = packs
+        return rest + [cmd]
 
     def _make_desc(self, spec):
         kind = getattr(spec, "kind", "conv")
@@ -1352,6 +1355,7 @@ class Plan:
                 sp.x, sp.ldx = _Ptr(y), y.ld
                 sp.xf = _Ptr(tab, C.sizeof(L.mi_bnx) * [id(k_) for k_ in keys].index(id(bn)))
                 sp.xf_write, sp.xf_C = int(id(bn) not in seen), bn.i[3]
+                sp.xf_bn = bn       # (the symbolic BN_ACT_FWD behind the record: tests/plan_interp.py)
                 seen.add(id(bn))
                 nm = _Cmd(m.op, m.i, m.f, m.p, m.l, sp, m.tag)
                 nm.lane = m.lane
@@ -1429,9 +1433,13 @@ class Plan:
         if which == "fwd":
             self.fwd_list = cmds
         self.cmd_descs[which] = [None] * len(cmds)
-        # symbolic builder commands behind a merged launch (None: the command is its own member); tests/plan_interp.py runs those
+        # symbolic builder commands behind a merged launch (None: the command is its own member); tests/plan_interp.py runs those.
+        # `parts`: the members of a launch whose operands live in a device job table only (PACK_W_BATCH, WGRAD_GROUP) - kept
+        # out of `members`, which _cmd_bufs / _defer_bn read
         self.cmd_members = getattr(self, "cmd_members", {})
-        self.cmd_members[which] = [getattr(c, "members", None) for c in cmds]
+        self.cmd_members[which] = [getattr(c, "members", None) or getattr(c, "parts", None) for c in cmds]
+        self.cmd_objs = getattr(self, "cmd_objs", {})
+        self.cmd_objs[which] = list(cmds)
         for k, c in enumerate(cmds):
             m = arr[k]
             m.op = c.op
