@@ -1046,6 +1046,27 @@ int mi_padding_masks(const int64_t* sizes_dev, int B, int nlev, void* const* out
 int mi_mask_targets_batch(const mi_mask_job* jobs, int B, int cap, int Hi, int Wi, int Ho, int Wo, float* tgt, void* tgtT_bf16,
                           int64_t* labels, float* t2, float* t2_ws, mi_stream_t s);
 
+/* mi_polygon_masks: the polygon ground truth of a batch rasterised on the device (csrc/polygon_masks.hip) - per image the
+ *   masks BitMasks.from_polygon_masks(polygons, h, w) gives (yolov7/modeling/meta_arch/sparseinst.py:111-115; pycocotools'
+ *   rleFrPoly per ring, the union of an instance's rings), bit for bit: out uint8 [M][h][w] row-major, 0 / 1, written
+ *   completely.  verts: the image's rings one after the other as fp64 x0, y0, x1, y1, ...; ring_off: int32 [rings + 1], the
+ *   first VERTEX of every ring; inst_off: int32 [M + 1], the first RING of every instance - all three on the device, and the
+ *   two offset tables once more in host memory (`*_host`: the argument checks read these; the caller keeps both copies
+ *   equal).  Refused: a ring of fewer than 3 vertices, an instance without a ring, h > MI_POLY_MAX_H (a block keeps
+ *   2 x 64 columns x (h + 1) bits in LDS), null pointers where M > 0.  One launch per MI_FEED_MAX_IMAGES images, no
+ *   workspace, deterministic. */
+#define MI_POLY_MAX_H 3807
+typedef struct mi_poly_job {
+  const double* verts;
+  const int32_t* ring_off;
+  const int32_t* inst_off;
+  const int32_t* ring_off_host;
+  const int32_t* inst_off_host;
+  void* out;
+  int M, h, w, pad_;
+} mi_poly_job;
+int mi_polygon_masks(const mi_poly_job* jobs, int B, mi_stream_t s);
+
 /* ---- hardware probes used by tests (lane layouts of MFMA / LDS transpose read) */
 int mi_probe_mfma32(const void* a_bf16_32x16, const void* b_bf16_16x32, float* d_32x32, mi_stream_t s);
 int mi_probe_mfma16(const void* a_bf16_16x32, const void* b_bf16_32x16, float* d_16x16, mi_stream_t s);

@@ -35,7 +35,7 @@ from torch import nn
 from .. import _lib as L
 from ..d2shim import META_ARCH_REGISTRY, ImageList, Instances, build_backbone
 from ..ops import ConvPaddedFn, HostRing, WgradBatch, _ConvGeom, _conv_desc, _ld, _nhwc_v, _run_conv, nhwc_strided_ok, wgrad_can_defer
-from ..ops import feed_batch_enabled, mask_targets_batch, normalize_pad_batch, pack_images
+from ..ops import feed_batch_enabled, mask_targets_batch, normalize_pad_batch, pack_images, polygon_masks_batch
 from .transformer import _LinearFn, _conv1x1, _factor
 
 # ------------------------------------------------------------------------------------------------ small op wrappers
@@ -1177,6 +1177,19 @@ class SparseInst(nn.Module):
         return ImageList.from_tensors(images, 32)
 
     def prepare_targets(self, targets):
+        if self.mask_format == "polygon":
+            # sparseinst.py:111-115 (BitMasks.from_polygon_masks(gt_masks.polygons, h, w), pycocotools on the host, per
+            # instance): the vertices go up and the whole batch is rasterised on the device by one launch, bit for bit
+            polys = []
+            for t in targets:
+                p = t.gt_masks if t.has("gt_masks") else []
+                p = p.polygons if hasattr(p, "polygons") else p
+                if torch.is_tensor(p) or hasattr(p, "tensor"):
+                    raise TypeError("SparseInst: INPUT.MASK_FORMAT is \"polygon\" but gt_masks holds dense masks (pass the "
+                                    "polygons - PolygonMasks or nested lists - or set MASK_FORMAT to \"bitmask\")")
+                polys.append(p)
+            masks = polygon_masks_batch(polys, [t.image_size for t in targets], self.device)
+            return [{"labels": t.gt_classes.to(self.device), "masks": m} for t, m in zip(targets, masks)]
         new_targets = []
         for t in targets:
             h, w = t.image_size
@@ -1184,8 +1197,6 @@ class SparseInst(nn.Module):
                 gt_masks = torch.empty(0, h, w)
             else:
                 gt_masks = t.gt_masks
-                if self.mask_format == "polygon":
-                    raise NotImplementedError("SparseInst: INPUT.MASK_FORMAT bitmask (Base-SparseInst.yaml:34)")
                 gt_masks = gt_masks.tensor if hasattr(gt_masks, "tensor") else gt_masks
             new_targets.append({"labels": t.gt_classes.to(self.device), "masks": gt_masks.to(self.device)})
         return new_targets

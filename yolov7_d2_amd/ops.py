@@ -229,6 +229,92 @@ def mask_targets_batch(masks, labels, cap, in_shape, out_shape, tgt, tgtT=None, 
             "mi_mask_targets_batch")
 
 
+POLYGON_MAX_COORD = float(1 << 20)      # |x|, |y| of a vertex: the walk along an edge is 5 steps per pixel of its length
+
+
+def _polygon_tables(polygons):
+    """host half of polygon_masks_batch: per image (vertices fp64 [2 * n], ring_off int32 [rings + 1], inst_off int32
+    [M + 1]); ValueError for a ring that is no polygon"""
+    import numpy as np
+    tables = []
+    for b, insts in enumerate(polygons):
+        insts = insts.polygons if hasattr(insts, "polygons") else insts
+        verts, ring_off, inst_off = [], [0], [0]
+        for i, rings in enumerate(insts):
+            if len(rings) == 0:
+                raise ValueError(f"polygon_masks_batch: image {b}, instance {i} has no ring")
+            if np.ndim(rings[0]) == 0:
+                raise ValueError(f"polygon_masks_batch: image {b}, instance {i}: an instance is a LIST of rings [x0, y0, x1, y1, ...]")
+            for r in rings:
+                r = np.asarray(r, dtype=np.float64).reshape(-1)
+                if r.size % 2 != 0 or r.size < 6:
+                    raise ValueError(f"polygon_masks_batch: image {b}, instance {i}: a ring of {r.size} numbers (x, y pairs of at "
+                                     "least 3 vertices)")
+                if not (np.abs(r) <= POLYGON_MAX_COORD).all():        # (also refuses NaN / inf)
+                    raise ValueError(f"polygon_masks_batch: image {b}, instance {i}: a coordinate beyond +-{POLYGON_MAX_COORD:.0f}")
+                verts.append(r)
+                ring_off.append(ring_off[-1] + r.size // 2)
+            inst_off.append(len(ring_off) - 1)
+        tables.append((np.concatenate(verts) if verts else np.zeros(0, np.float64), np.asarray(ring_off, np.int32),
+                       np.asarray(inst_off, np.int32)))
+    return tables
+
+
+def polygon_masks_batch(polygons, sizes, device):
+    """the polygon ground truth of a batch as dense masks, rasterised ON THE DEVICE in one launch (mi_polygon_masks): per image
+    what BitMasks.from_polygon_masks(polygons, h, w) gives in the reference (meta_arch/sparseinst.py:111-115 - pycocotools'
+    rleFrPoly per ring, the union of an instance's rings), bit for bit.
+
+    polygons: per image a list of instances (or an object with `.polygons`), an instance a list of rings, a ring a flat
+    sequence / ndarray [x0, y0, x1, y1, ...] of at least 3 vertices in pixel coordinates (outside the image is fine);
+    sizes: per image (h, w).  Returns per image a uint8 tensor [M, h, w] of 0 / 1 on `device` ([0, h, w] for no instance).
+    The vertices and offsets of the whole batch go up in ONE transfer from page-locked memory (HostRing); nothing waits
+    for the device."""
+    import numpy as np
+    device = torch.device(device)
+    B = len(polygons)
+    if len(sizes) != B:
+        raise ValueError(f"polygon_masks_batch: {B} images, {len(sizes)} sizes")
+    tables = _polygon_tables(polygons)
+    sizes = [(int(s[0]), int(s[1])) for s in sizes]
+    if device.type != "cuda":
+        raise L.MI355Error(f"polygon_masks_batch on {device}: the rasteriser is a HIP kernel (no CPU fallback)")
+    outs = [torch.empty((len(io) - 1, h, w), dtype=torch.uint8, device=device) for (_, _, io), (h, w) in zip(tables, sizes)]
+    if B == 0 or all(len(io) == 1 for _, _, io in tables):
+        return outs
+    if torch.cuda.is_current_stream_capturing():
+        raise L.MI355Error("polygon_masks_batch inside a graph capture: ground truth belongs to the eager half (prepare_batch)")
+    # one page-locked slot: [vertices of all images | ring offsets | instance offsets], 8-byte pieces first
+    nbytes, where = 0, []
+    for v, ro, io in tables:
+        where.append([nbytes])
+        nbytes += v.nbytes
+    for k in (1, 2):
+        for b, t in enumerate(tables):
+            where[b].append(nbytes)
+            nbytes += _rup(t[k].nbytes, 8)
+    with torch.cuda.device(device):
+        slot = HostRing._take(nbytes)[:nbytes]
+        host = slot.numpy()
+        for t, offs in zip(tables, where):
+            for a, o in zip(t, offs):
+                host[o:o + a.nbytes] = a.view(np.uint8)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        buf.copy_(slot, non_blocking=True)
+        jobs = (L.mi_poly_job * B)()
+        hp, dp = slot.data_ptr(), buf.data_ptr()
+        for b, ((v, ro, io), offs, (h, w)) in enumerate(zip(tables, where, sizes)):
+            j = jobs[b]
+            j.M, j.h, j.w = len(io) - 1, h, w
+            if j.M == 0:
+                continue
+            j.verts, j.ring_off, j.inst_off = dp + offs[0], dp + offs[1], dp + offs[2]
+            j.ring_off_host, j.inst_off_host = hp + offs[1], hp + offs[2]
+            j.out = outs[b].data_ptr()
+        L.check(L.lib().mi_polygon_masks(jobs, B, L.stream_ptr()), "mi_polygon_masks")
+    return outs
+
+
 # ------------------------------------------------------------------------------------------------ grouped weight gradients
 class WgradBatch:
     """Weight gradients of the eager module trees (transformer Linears, ResNet convolutions), deferred and issued ONE
