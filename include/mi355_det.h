@@ -1067,6 +1067,49 @@ typedef struct mi_poly_job {
 } mi_poly_job;
 int mi_polygon_masks(const mi_poly_job* jobs, int B, mi_stream_t s);
 
+/* ---- SparseInst inference postprocess for a whole batch (csrc/sparseinst_infer.hip): what SparseInst.inference
+ * (yolov7/modeling/meta_arch/sparseinst.py:169-234 + rescoring_mask :24-27) computes in a per-image loop of torch ops, in three
+ * launches and one host read-back (the counts).  No fp32 mask intermediate is written to memory.
+ *
+ * The mask logits are read IN PLACE: `masks` + element strides (sb, sq, sy, sx) for (image, query, row, column), all >= 1
+ * (sb >= 0), mask_dtype 0 = fp32, 1 = bf16 - the decoder's NHWC bf16 tensor [B][h][w][Np] is (h * w * Np, 1, w * Np, Np), a dense
+ * fp32 [B][N][h][w] is (N * h * w, h * w, w, 1).  Only queries 0 .. N - 1 are read.
+ *
+ * mi_sparseinst_infer_select: for every (b, q)
+ *     score = max_c sqrt(sigmoid(logits[b][q][c]) * sigmoid(obj[b][q])), label = the FIRST maximum (torch.max), keep = score > cls_thr;
+ *   the kept queries of an image are compacted in ascending q (the order of boolean-mask indexing), and each is rescored over
+ *   the whole h x w prediction, padding included: m = sigmoid(float(mask)),
+ *     score *= sum(m * (m > mask_thr)) / (sum(m > mask_thr) + 1e-6)            (fp32 sums in a fixed order: deterministic).
+ *   logits fp32 [B][N][C], obj fp32 [B][N], both dense.  Outputs: counts int32 [B]; kept_query int32 [B][N], scores fp32 [B][N],
+ *   labels int64 [B][N] - the first counts[b] entries of row b, the rest is left as it was.  ws: mi_sparseinst_infer_ws_bytes(B,
+ *   N, h, w) = B * ceil(h * w / 256) * 2 * N * 4 bytes (the per-chunk partial sums), 4-byte aligned.  Two launches, no host sync.
+ * mi_sparseinst_infer_masks: for image b and its j-th kept query q = kept_query[b][j], j < descs[b].n, every pixel (oy, ox) of
+ *   out[descs[b].out_off + (j * Hout + oy) * Wout + ox] = value > mask_thr ? 1 : 0   (one byte), value being the composition
+ *     bilinear (h, w) -> (Hpad, Wpad), crop to (h_img, w_img), bilinear -> (Hout, Wout)   of sigmoid(mask), in fp32,
+ *   with ATen's align_corners=False arithmetic on both levels: scale = float(in) / float(out), src = max(0, scale * (dst + 0.5)
+ *   - 0.5), i0 = min(int(src), in - 1), i1 = min(i0 + 1, in - 1), l = src - int(src), value = (1 - ly) * ((1 - lx) * a + lx * b) +
+ *   ly * ((1 - lx) * c + lx * d).  The outer level's `in` is the cropped size (h_img, w_img), so its indices never leave the
+ *   crop; each of its 2 x 2 samples is the inner level's 2 x 2 interpolation (in = (h, w), out = (Hpad, Wpad)), a complete fp32
+ *   value before the outer level uses it.  `descs` is a HOST array of B records, passed on by value (MI_FEED_MAX_IMAGES images
+ *   per launch); an image with n == 0 writes nothing.  sigmoid is evaluated once per source pixel of a block's tile and kept
+ *   in LDS; an image whose total down-scale makes a tile's source rectangle exceed that stage reads its taps from memory.
+ * Refused before any launch (-1, mi_last_error): null pointers; B < 0; N, C, h or w < 1; Hpad or Wpad < 1; a mask dtype other
+ *   than 0 / 1 or a stride < 1; a descriptor with n outside 0 .. N, or - where n > 0 - Hout or Wout < 1, h_img or w_img < 1 or
+ *   beyond (Hpad, Wpad), or n * Hout * Wout bytes at out_off not inside out_bytes; a workspace smaller than the size query.
+ *   B == 0 returns 0 without a launch. */
+typedef struct mi_sparseinst_infer_desc {
+  int64_t out_off;                    /* byte offset of the image's [n][Hout][Wout] block in `out` */
+  int32_t n, h_img, w_img, Hout, Wout, pad_;
+} mi_sparseinst_infer_desc;
+int64_t mi_sparseinst_infer_ws_bytes(int B, int N, int h, int w);          /* -1: B < 0 or N, h, w < 1 */
+int mi_sparseinst_infer_select(const float* logits, const float* obj, const void* masks, int mask_dtype, int64_t sb, int64_t sq,
+                               int64_t sy, int64_t sx, int B, int N, int C, int h, int w, float cls_thr, float mask_thr,
+                               int* counts, int* kept_query, float* scores, int64_t* labels, void* ws, int64_t ws_bytes,
+                               mi_stream_t s);
+int mi_sparseinst_infer_masks(const void* masks, int mask_dtype, int64_t sb, int64_t sq, int64_t sy, int64_t sx, int B, int N,
+                              int h, int w, int Hpad, int Wpad, const int* kept_query, const mi_sparseinst_infer_desc* descs,
+                              float mask_thr, void* out, int64_t out_bytes, mi_stream_t s);
+
 /* ---- hardware probes used by tests (lane layouts of MFMA / LDS transpose read) */
 int mi_probe_mfma32(const void* a_bf16_32x16, const void* b_bf16_16x32, float* d_32x32, mi_stream_t s);
 int mi_probe_mfma16(const void* a_bf16_16x32, const void* b_bf16_32x16, float* d_16x16, mi_stream_t s);

@@ -177,6 +177,10 @@ class mi_poly_job(C.Structure):
                 ("inst_off_host", C.c_void_p), ("out", C.c_void_p), ("M", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("pad_", C.c_int32)]
 
 
+class mi_sparseinst_infer_desc(C.Structure):
+    _fields_ = [("out_off", C.c_int64)] + [(n, C.c_int32) for n in ("n", "h_img", "w_img", "Hout", "Wout", "pad_")]
+
+
 class mi_mosaic_paste_job(C.Structure):
     _fields_ = [("src", C.c_void_p), ("canvas", C.c_void_p)] + [(n, C.c_int32) for n in
                 ("h0", "w0", "rh", "rw", "cw", "x1a", "y1a", "x2a", "y2a", "x1b", "y1b", "blk0", "fsrc", "pad_")]
@@ -384,6 +388,10 @@ _PROTOS = {
     "mi_normalize_pad_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "mi_mask_targets_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi_polygon_masks": (C.c_int, [_vp, C.c_int, _vp]),
+    "mi_sparseinst_infer_ws_bytes": (C.c_int64, [_i, _i, _i, _i]),
+    "mi_sparseinst_infer_select": (C.c_int, [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp,
+                                             _vp, _i64, _vp]),
+    "mi_sparseinst_infer_masks": (C.c_int, [_vp, _i, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i64, _vp]),
     "mi_graph_capture": (C.c_int64, [C.POINTER(mi_cmd), _i, _vp]),
     "mi_graph_launch": (C.c_int, [_i64, _vp]),
     "mi_graph_destroy": (C.c_int, [_i64]),

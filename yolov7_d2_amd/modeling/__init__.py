@@ -18,7 +18,7 @@ from .detr_meta import (Detr, Joiner, MaskedBackbone, MaskedBackboneTraceFriendl
 from .sparseinst import (SparseInst, InstanceContextEncoder, PyramidPoolingModule, MyAdaptiveAvgPool2d, InstanceBranch,
                          GroupInstanceBranch, MaskBranch, BaseIAMDecoder, GroupIAMDecoder, SparseInstCriterion,
                          SparseInstMatcher, build_sparse_inst_encoder, build_sparse_inst_decoder,
-                         build_sparse_inst_criterion, rescoring_mask)
+                         build_sparse_inst_criterion, rescoring_mask, sparseinst_inference_batched)
 from .yolov6_loss import ComputeLoss
 from .bifpn import (BiFPN, BiFpnLayer, FpnCombine, ResampleFeatureMap, SeparableConv2d, ConvBnAct2d, Swish, GroupNorm,
                     get_fpn_config, build_resnet_bifpn_backbone)

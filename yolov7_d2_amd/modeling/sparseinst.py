@@ -27,6 +27,7 @@ device ops.  No CPU path: device tensors only.
 """
 import ctypes as C
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -1148,6 +1149,80 @@ def rescoring_mask(scores, mask_pred, masks):
     return scores * ((masks * mask_pred_).sum([1, 2]) / (mask_pred_.sum([1, 2]) + 1e-6))
 
 
+# MI_SPARSEINST_INFER_BATCHED=0: eval-mode forward takes the reference's per-image loop (SparseInst.inference) instead of
+# sparseinst_inference_batched (A/B, tests); read once, here
+_INFER_BATCHED = os.environ.get("MI_SPARSEINST_INFER_BATCHED", "1") != "0"
+
+
+@torch.no_grad()
+def sparseinst_inference_batched(output, image_sizes, out_sizes, max_shape, cls_threshold, mask_threshold):
+    """SparseInst.inference for all B images at once (csrc/sparseinst_infer.hip): three launches and ONE host read-back, the
+    B kept-counts; no fp32 mask intermediate is written (the loop: sigmoid of all B x N masks in fp32, then per image a
+    boolean-mask index - a host sync -, two F.interpolate results in fp32 and a compare).
+
+    output: the decoder's dict - `pred_logits` [B, N, C], `pred_scores` [B, N, 1] and the mask logits, read in place through
+    their strides: `_masks_nhwc` (bf16 [B, h, w, Np], query = channel) when present, else `pred_masks` [B, N, h, w] (fp32 or
+    bf16, any strides).  image_sizes / out_sizes: per image (h, w) before padding / of the requested result; max_shape: the
+    padded batch shape.  Returns per image an Instances(out_size) with `scores` fp32 [n], `pred_classes` int64 [n] and
+    `pred_masks` bool [n, Hout, Wout] - views into one flat result - in ascending query order; an image that keeps no query
+    has empty `scores` / `pred_classes` and no `pred_masks`, as in the loop."""
+    logits = output["pred_logits"].float().contiguous()
+    B, N, Cc = logits.shape
+    dev = logits.device
+    if dev.type != "cuda":
+        raise L.MI355Error(f"sparseinst_inference_batched on {dev}: the postprocess is HIP kernels (no CPU fallback)")
+    if not (len(image_sizes) == len(out_sizes) == B):
+        raise ValueError(f"sparseinst_inference_batched: {B} images, {len(image_sizes)} image sizes, {len(out_sizes)} output sizes")
+    obj = output["pred_scores"].float().reshape(B, N).contiguous()
+    if output.get("_masks_nhwc") is not None:
+        masks = output["_masks_nhwc"].permute(0, 3, 1, 2)         # [B, Np, h, w] view, Np >= N
+    else:
+        masks = output["pred_masks"]
+    if masks.dtype not in (torch.float32, torch.bfloat16):
+        masks = masks.float()
+    if masks.dim() != 4 or masks.shape[0] != B or masks.shape[1] < N or masks.device != dev:
+        raise ValueError(f"sparseinst_inference_batched: mask logits {tuple(masks.shape)} on {masks.device} for {B} x {N} queries on {dev}")
+    h, w = int(masks.shape[2]), int(masks.shape[3])
+    if B > 0 and min(masks.stride()[1:]) < 1:
+        masks = masks.contiguous()
+    margs = (masks.data_ptr(), 0 if masks.dtype == torch.float32 else 1) + tuple(int(v) for v in masks.stride())
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        counts = torch.empty(B, dtype=torch.int32, device=dev)
+        kept = torch.empty(B, N, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, N, dtype=torch.float32, device=dev)
+        labels = torch.empty(B, N, dtype=torch.int64, device=dev)
+        ws_bytes = L.check(lib.mi_sparseinst_infer_ws_bytes(B, N, h, w), "mi_sparseinst_infer_ws_bytes")
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+        L.check(lib.mi_sparseinst_infer_select(logits.data_ptr(), obj.data_ptr(), *margs, B, N, Cc, h, w, float(cls_threshold),
+                                               float(mask_threshold), counts.data_ptr(), kept.data_ptr(), scores.data_ptr(),
+                                               labels.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()),
+                "mi_sparseinst_infer_select")
+        n = counts.tolist()                                       # the one read-back
+        descs = (L.mi_sparseinst_infer_desc * max(B, 1))()
+        total = 0
+        for b in range(B):
+            d = descs[b]
+            d.out_off, d.n = total, n[b]
+            d.h_img, d.w_img = int(image_sizes[b][0]), int(image_sizes[b][1])
+            d.Hout, d.Wout = int(out_sizes[b][0]), int(out_sizes[b][1])
+            total += n[b] * d.Hout * d.Wout
+        flat = torch.empty(total, dtype=torch.uint8, device=dev)
+        if total:
+            L.check(lib.mi_sparseinst_infer_masks(*margs, B, N, h, w, int(max_shape[0]), int(max_shape[1]), kept.data_ptr(), descs,
+                                                  float(mask_threshold), flat.data_ptr(), total, L.stream_ptr()),
+                    "mi_sparseinst_infer_masks")
+    results = []
+    for b in range(B):
+        d = descs[b]
+        r = Instances((d.Hout, d.Wout))
+        if n[b]:
+            r.pred_masks = flat[d.out_off: d.out_off + n[b] * d.Hout * d.Wout].view(n[b], d.Hout, d.Wout).view(torch.bool)
+        r.scores, r.pred_classes = scores[b, : n[b]], labels[b, : n[b]]
+        results.append(r)
+    return results
+
+
 @META_ARCH_REGISTRY.register()
 class SparseInst(nn.Module):
     def __init__(self, cfg):
@@ -1263,8 +1338,15 @@ class SparseInst(nn.Module):
             pk = _pack_targets(self.prepare_targets(gt_instances), max_shape, output["_masks_nhwc"].shape[1:3], self.device,
                                cap=self._capacity(batched_inputs))
             return self.criterion(output, pk)
-        results = self.inference(output, batched_inputs, max_shape, images.image_sizes)
+        infer = self.inference_batched if _INFER_BATCHED else self.inference
+        results = infer(output, batched_inputs, max_shape, images.image_sizes)
         return [{"instances": r} for r in results]
+
+    @torch.no_grad()
+    def inference_batched(self, output, batched_inputs, max_shape, image_sizes):
+        """`inference` for the whole batch in three launches and one read-back (sparseinst_inference_batched)"""
+        out_sizes = [(inp.get("height", s[0]), inp.get("width", s[1])) for inp, s in zip(batched_inputs, image_sizes)]
+        return sparseinst_inference_batched(output, image_sizes, out_sizes, max_shape, self.cls_threshold, self.mask_threshold)
 
     @torch.no_grad()
     def inference(self, output, batched_inputs, max_shape, image_sizes):
