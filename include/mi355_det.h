@@ -386,6 +386,16 @@ int mi_maxpool3x3s2_bwd_idx(const uint8_t* code, const void* dy, int lddy, void*
                             int W, int C, mi_stream_t s);
 int mi_maxpool3x3s2_bwd(const void* x, int ldx, const void* dy, int lddy, void* dx, int lddx, int accumulate, int N,
                         int H, int W, int C, mi_stream_t s);
+/* nn.AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) in front of a ResNet-vd projection shortcut
+ * (yolov7/modeling/backbone/resnetvd.py:157-182 downsample_avg), bf16 NHWC views, C %% 8 == 0, pixel strides multiples of 8,
+ * 16-byte aligned pointers.  outH = (H + 1) / 2, outW = (W + 1) / 2.  Forward: the fp32 sum, in row-major window order, of
+ * the 1, 2 or 4 inputs inside the map, divided by that count, rounded once to bf16.  Backward: EVERY input pixel (iy, ix)
+ * is written: dx = dy[iy / 2][ix / 2] / count (+ the value already in dx when accumulate != 0, added in fp32), rounded once
+ * to bf16, then zeroed where mask <= 0 when mask != NULL (mask: the ReLU output the pooled map was taken from; the bits of
+ * mi_ew_bf16 op 2 applied afterwards). */
+int mi_avgpool2x2s2_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, mi_stream_t s);
+int mi_avgpool2x2s2_bwd(const void* dy, int lddy, void* dx, int lddx, const void* mask, int ldmask, int accumulate, int N,
+                        int H, int W, int C, mi_stream_t s);
 /* generic strided bf16 NHWC copy / accumulate (dst (+)= src) */
 int mi_copy_bf16(const void* src, int lds_, void* dst, int ldd, int accumulate, int64_t npix, int C,
                  mi_stream_t s);

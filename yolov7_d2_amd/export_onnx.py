@@ -316,6 +316,10 @@ class _NetEmitter:
     # ---- detectron2 ResNet (modeling/resnet.py; the reference builds it with d2's build_resnet_backbone)
     def resnet(self, bb, x, scope):
         g = self.g
+        if type(bb).__name__ == "ResNetVD":
+            # timm's resnet50d / resnet101d (modeling/resnet_vd.py): deep stem and pooled shortcuts are not written here
+            raise NotImplementedError("export_onnx: no emitter for the ResNet-vd backbone (build_resnet_vd_backbone, ResNetVD): "
+                                      "only detectron2's ResNet (build_resnet_backbone) is exported")
         x = self.conv(bb.stem.conv1, x, scope + ".stem.conv1", relu=True)
         x = g.node("MaxPool", [x], scope + ".stem", ceil_mode=0, dilations=[1, 1], kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[2, 2])
         outs = {}

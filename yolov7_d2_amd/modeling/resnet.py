@@ -162,37 +162,43 @@ class Conv2d(nn.Module):
         The frozen affine is folded into the packed weight image (scale) and the bias (shift).
         add_relu (no-autograd path only): an NCHW tensor of the output's shape; returns relu(bf16(conv + shift) + add_relu) from
         the convolution's epilogue (MI_CONV_ADDRELU): conv3 + shortcut + ReLU of a frozen bottleneck as one launch"""
-        scale, shift = self.norm.affine()
-        if add_relu is not None and (not _FOLDED_FN() or (self.weight.requires_grad and torch.is_grad_enabled())
-                                     or (x.requires_grad and torch.is_grad_enabled())):
-            raise L.MI355Error("Conv2d.forward(add_relu=...): only on the frozen / no-autograd path")
-        if not _FOLDED_FN():
-            w = self.weight * scale.view(-1, 1, 1, 1)
-            op = torch.ops.mi355.conv2d_relu if relu else torch.ops.mi355.conv2d
-            if not self.weight.requires_grad:
-                with torch.no_grad():
-                    return op(x, w, shift, self.stride, self.padding)
-            return op(x, w, shift, self.stride, self.padding)
-        train_w = self.weight.requires_grad and torch.is_grad_enabled()
-        if not train_w and not (x.requires_grad and torch.is_grad_enabled()):
-            g = _ConvGeom(x.shape, self.weight.shape, self.stride, self.padding)
+        return conv_norm_forward(self, self.weight, self.norm, self.stride, self.padding, x, relu, add_relu)
+
+
+def conv_norm_forward(owner, weight, norm, stride, padding, x, relu=False, add_relu=None):
+    """Conv2d.forward for any (OIHW weight, FrozenBatchNorm2d) pair - modeling/resnet_vd.py keeps them in separate modules
+    under timm's names.  owner: the module whose __dict__ keeps the frozen layer's packed image"""
+    scale, shift = norm.affine()
+    if add_relu is not None and (not _FOLDED_FN() or (weight.requires_grad and torch.is_grad_enabled())
+                                 or (x.requires_grad and torch.is_grad_enabled())):
+        raise L.MI355Error("Conv2d.forward(add_relu=...): only on the frozen / no-autograd path")
+    if not _FOLDED_FN():
+        w = weight * scale.view(-1, 1, 1, 1)
+        op = torch.ops.mi355.conv2d_relu if relu else torch.ops.mi355.conv2d
+        if not weight.requires_grad:
             with torch.no_grad():
-                if self.weight.requires_grad:
-                    # a TRAINABLE layer run without autograd (evaluation between training steps): packed per call - its
-                    # weight may have been updated by a kernel that torch's version counter does not see
-                    # (mi_adamw_step_multi, the arena SGD), so no key could tell a stale image from a fresh one
-                    wf = g.pack(self.weight, dgrad=False, scale=scale)[0]
-                else:
-                    # a frozen layer under a frozen prefix (FREEZE_AT): its packed image is a constant too.  Keyed on the
-                    # identity + write counters of the weight and of the four norm buffers (load_state_dict / .to() change
-                    # them), not on the address of `scale`: a recomputed scale may be handed the freed one's address
-                    key = (self.weight.data_ptr(), self.weight._version, self.norm.__dict__["_affine"][0])
-                    c = self.__dict__.get("_image")
-                    if c is None or c[0] != key:
-                        c = self.__dict__["_image"] = (key, _same_address(c, g.pack(self.weight, dgrad=False, scale=scale)[0]))
-                    wf = c[1]
-                return _folded_forward(g, x, wf, shift, relu, add_relu)[1]
-        return _FoldedConvFn.apply(x, self.weight, scale, shift, self.stride, self.padding, relu)
+                return op(x, w, shift, stride, padding)
+        return op(x, w, shift, stride, padding)
+    train_w = weight.requires_grad and torch.is_grad_enabled()
+    if not train_w and not (x.requires_grad and torch.is_grad_enabled()):
+        g = _ConvGeom(x.shape, weight.shape, stride, padding)
+        with torch.no_grad():
+            if weight.requires_grad:
+                # a TRAINABLE layer run without autograd (evaluation between training steps): packed per call - its
+                # weight may have been updated by a kernel that torch's version counter does not see
+                # (mi_adamw_step_multi, the arena SGD), so no key could tell a stale image from a fresh one
+                wf = g.pack(weight, dgrad=False, scale=scale)[0]
+            else:
+                # a frozen layer under a frozen prefix (FREEZE_AT): its packed image is a constant too.  Keyed on the
+                # identity + write counters of the weight and of the four norm buffers (load_state_dict / .to() change
+                # them), not on the address of `scale`: a recomputed scale may be handed the freed one's address
+                key = (weight.data_ptr(), weight._version, norm.__dict__["_affine"][0])
+                c = owner.__dict__.get("_image")
+                if c is None or c[0] != key:
+                    c = owner.__dict__["_image"] = (key, _same_address(c, g.pack(weight, dgrad=False, scale=scale)[0]))
+                wf = c[1]
+            return _folded_forward(g, x, wf, shift, relu, add_relu)[1]
+    return _FoldedConvFn.apply(x, weight, scale, shift, stride, padding, relu)
 
 
 def _same_address(cached, new):
