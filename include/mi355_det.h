@@ -197,7 +197,7 @@ typedef struct mi_wgrad_desc {
   int32_t stride;
   int32_t Cin, Cout;        /* real channel counts written to gw              */
   int32_t CinPad, CoutPad;  /* readable (zero-padded) channels, CinPad%16==0, CoutPad%32==0 */
-  int32_t ntaps;            /* 1 or 9 */
+  int32_t ntaps;            /* 1, 9 or 16 (MI_MAX_TAPS: the ResNet stem's 4x4 table); any (tap_dy, tap_dx) per tap */
   int32_t tap_dy[MI_MAX_TAPS], tap_dx[MI_MAX_TAPS];
   int32_t accumulate;
   int32_t TH, TW, splitk, cfg_tp, cfg_ns; /* 0 => chosen by launcher (pixel tile, split-K, tile pixels, LDS stages) */
