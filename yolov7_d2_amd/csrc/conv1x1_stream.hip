@@ -225,6 +225,15 @@ static bool c1s_launch_any(const mi_conv_desc* ds, int n, hipStream_t s, int* rc
 }
 bool c1s_try_launch(const mi_conv_desc* ds, int n, hipStream_t s, int* rc) { return c1s_enabled() && c1s_launch_any(ds, n, s, rc); }
 bool c1s_try_plan(const mi_conv_desc* ds, int n, C1Launch* l) { return c1s_enabled() && c1s_fill(ds, n, l); }
+// does mi_conv2d run this descriptor here?  c1s_launch_any's decision without the launch: one launch, or - more output
+// channels than a slice table holds - 512 at a time (the first chunk decides)
+bool c1s_try_route(const mi_conv_desc* d) {
+  if (!c1s_enabled()) return false;
+  C1Launch l;
+  const int step = 32 * C1_MAX_SLICES;
+  if (d->Cout > step && d->Cout % step == 0 && !d->stats_acc && !d->xf) return c1s_fill(d, 1, &l, nullptr, 0, step);
+  return c1s_fill(d, 1, &l);
+}
 bool c1s_try_plan_bn(const mi_conv_desc* ds, const mi_bn_job* bn, int n, C1Launch* l) { return c1s_enabled() && c1s_fill(ds, n, l, bn); }
 int c1s_barrier_status(unsigned* flag) { return c1s_bar_status(flag); }
 int c1s_run_planned(const C1Launch* l, hipStream_t s) { return c1s_run(*l, s); }

@@ -33,6 +33,7 @@
 // streaming 1x1 path (conv1x1_stream.hip): eligible descriptors leave the tile kernel
 bool c1s_try_launch(const mi_conv_desc* ds, int n, hipStream_t s, int* rc);
 bool c1s_try_plan(const mi_conv_desc* ds, int n, C1Launch* l);
+bool c1s_try_route(const mi_conv_desc* d);
 int c1s_run_planned(const C1Launch* l, hipStream_t s);
 bool c1s_try_plan_bn(const mi_conv_desc* ds, const mi_bn_job* bn, int n, C1Launch* l);
 int c1s_barrier_status(unsigned* flag);
@@ -260,8 +261,7 @@ static int conv_fill(const mi_conv_desc* d, ConvK* k, ConvCfg* c, size_t* ldsByt
 // which kernel family mi_conv2d runs for this descriptor: 0 tile (conv_igemm), 1 streaming 1x1, 2 weight-stationary 3x3
 extern "C" int mi_conv2d_route(const mi_conv_desc* d) {
   MI_REQUIRE(d, "conv2d_route: null");
-  C1Launch cl;
-  if (c1s_try_plan(d, 1, &cl)) return 1;
+  if (c1s_try_route(d)) return 1;   // (a layer of more than 512 output channels included: several streaming launches)
   W3Launch wl;
   if (w3_try_plan(d, 1, &wl)) return 2;
   return d->xf ? -1 : 0;   // (no kernel applies the input BatchNorm on the tile path: -1 without an error record)
