@@ -396,6 +396,28 @@ int mi_maxpool3x3s2_bwd(const void* x, int ldx, const void* dy, int lddy, void* 
 int mi_avgpool2x2s2_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, mi_stream_t s);
 int mi_avgpool2x2s2_bwd(const void* dy, int lddy, void* dx, int lddx, const void* mask, int ldmask, int accumulate, int N,
                         int H, int W, int C, mi_stream_t s);
+/* ---- deformable 3x3 convolution, staged (csrc/deform_conv.hip): detectron2's DeformConv, unmodulated, one deformable
+ * group, groups 1.  bf16 NHWC maps, C %% 32 == 0.  offset: bf16 NHWC with pixel stride ldoff >= 18, read where the offset
+ * convolution wrote it; for tap t = i*3 + j channel 2t is the row offset, 2t + 1 the column offset.  Sample point of output
+ * pixel (ho, wo): h = ho*stride - pad + i*dil + off_h (w alike); it counts only if h > -1 && w > -1 && h < H && w < W, the cell
+ * is floor(h), floor(h) + 1, a corner outside [0, H-1] x [0, W-1] contributes zero, interpolation in fp32.
+ * Served: stride 1 or 2, pad 1, dil 1 (outH = (H - 1) / stride + 1); anything else returns MI_EINVAL and launches nothing.
+ * mi_deform_im2col: col[N*outH*outW][9*C] bf16, tap-major with the C channels of a tap contiguous; the convolution is then the
+ *   1x1 convolution of col with the weight permuted to [Cout][tap][C] (mi_conv2d).
+ * mi_deform_col2im: from dcol (the 1x1 data gradient, col's layout), x and offset: d_offset[N][outH][outW][32] bf16 (fp32 sums
+ *   over C; channels 18..31 written as zero; a sample at an integer coordinate takes the right-hand difference) and
+ *   dx32[N][H][W][C] += dcol * corner weight with fp32 atomics (clear it with mi_deform_zero_f32 first).  grid_max: NULL, or
+ *   a device float holding max |dcol| (mi_deform_absmax into a zeroed float): every addend is then rounded to a multiple of
+ *   2^(e - 16), 2^e >= that maximum, so that the additions are exact and the sums do not depend on the order the atomics
+ *   arrive in (bit-reproducible dx; up to 256 addends of the largest magnitude per element).
+ * mi_deform_dx_finish: dx = bf16(dx32), zeroed where mask <= 0 when mask != NULL (mask: the ReLU output x was; mi_ew_bf16 op 2). */
+int mi_deform_im2col(const void* x, int ldx, const void* offset, int ldoff, void* col, int N, int H, int W, int C, int stride,
+                     int pad, int dil, mi_stream_t s);
+int mi_deform_col2im(const void* dcol, const void* x, int ldx, const void* offset, int ldoff, float* dx32, void* d_offset,
+                     const float* grid_max, int N, int H, int W, int C, int stride, int pad, int dil, mi_stream_t s);
+int mi_deform_absmax(const void* v, int64_t n, float* out, mi_stream_t s);
+int mi_deform_zero_f32(float* p, int64_t n, mi_stream_t s);
+int mi_deform_dx_finish(const float* dx32, const void* mask, int ldmask, void* dx, int lddx, int64_t npix, int C, mi_stream_t s);
 /* generic strided bf16 NHWC copy / accumulate (dst (+)= src) */
 int mi_copy_bf16(const void* src, int lds_, void* dst, int ldd, int accumulate, int64_t npix, int C,
                  mi_stream_t s);

@@ -264,6 +264,11 @@ _PROTOS = {
     "mi_maxpool3x3s2_bwd_idx": (C.c_int, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mi_avgpool2x2s2_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "mi_avgpool2x2s2_bwd": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mi_deform_im2col": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mi_deform_col2im": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mi_deform_absmax": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "mi_deform_zero_f32": (C.c_int, [_vp, _i64, _vp]),
+    "mi_deform_dx_finish": (C.c_int, [_vp, _vp, _i, _vp, _i, _i64, _i, _vp]),
     "mi_upsample2x_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "mi_upsample2x_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mi_spp_pool_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

@@ -320,6 +320,10 @@ class _NetEmitter:
             # timm's resnet50d / resnet101d (modeling/resnet_vd.py): deep stem and pooled shortcuts are not written here
             raise NotImplementedError("export_onnx: no emitter for the ResNet-vd backbone (build_resnet_vd_backbone, ResNetVD): "
                                       "only detectron2's ResNet (build_resnet_backbone) is exported")
+        if any(type(m).__name__ == "DeformConv" for m in bb.modules()):
+            # ONNX has no deformable convolution of this definition (opset 19's DeformConv is the modulated torchvision form)
+            raise NotImplementedError("export_onnx: the backbone holds a DeformConv (MODEL.RESNETS.DEFORM_ON_PER_STAGE): "
+                                      "deformable convolution is not exported")
         x = self.conv(bb.stem.conv1, x, scope + ".stem.conv1", relu=True)
         x = g.node("MaxPool", [x], scope + ".stem", ceil_mode=0, dilations=[1, 1], kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[2, 2])
         outs = {}

@@ -26,7 +26,7 @@ from torch import nn
 
 from .. import _lib as L
 from ..d2shim import BACKBONE_REGISTRY, Backbone, ShapeSpec
-from ..ops import WgradBatch, _ConvGeom, _conv_desc, _nchw, _nhwc, _nhwc_v, _pad_last, _run_conv, wgrad_can_defer
+from ..ops import WgradBatch, _ConvGeom, _conv_desc, _ld, _nchw, _nhwc, _nhwc_v, _pad_last, _run_conv, wgrad_can_defer
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -565,9 +565,191 @@ class BottleneckBlock(nn.Module):
         return _add_relu(out, sc)
 
 
-class ResNet(Backbone):
-    def __init__(self, depth=50, out_features=("res5",), freeze_at=2, stride_in_1x1=False):
+def _DEFORM_KEEP_COL():
+    """MI_DEFORM_KEEP_COL (default 1): a DeformConv keeps its sampled columns for the backward pass (9x its input, read once
+    by the weight gradient); 0 samples them again there - one more mi_deform_im2col per layer, nothing kept
+    (profiles/deform_conv_probe.txt has both)"""
+    return os.environ.get("MI_DEFORM_KEEP_COL", "1") != "0"
+
+
+def _offset_operand(offset, N, Ho, Wo):
+    """offset [N, 18, Ho, Wo] -> (tensor to keep alive, pixel stride): read IN PLACE when it is the channel slice of a bf16
+    NHWC map (what mi355::conv2d returns for 18 outputs: rows of 32), a padded NHWC copy otherwise"""
+    if tuple(offset.shape) != (N, 18, Ho, Wo):
+        raise L.MI355Error(f"DeformConv: offset {tuple(offset.shape)} is not [N, 18, Ho, Wo] = {(N, 18, Ho, Wo)}")
+    if offset.dtype == torch.bfloat16:
+        sn, sc, sh, sw = offset.stride()
+        if sc == 1 and sw >= 18 and (Ho == 1 or sh == Wo * sw) and (N == 1 or sn == Ho * Wo * sw):
+            return offset, sw
+    return _pad_last(_nhwc(offset.detach()), 32), 32
+
+
+def _deform_cols(xh, off, ldoff, Ho, Wo, stride):
+    """sampled im2col: bf16 [N, Ho, Wo, 9 * C], tap-major, the C channels of a tap contiguous"""
+    N, H, W, Cc = xh.shape
+    col = torch.empty(N, Ho, Wo, 9 * Cc, dtype=torch.bfloat16, device=xh.device)
+    L.check(L.lib().mi_deform_im2col(xh.data_ptr(), _ld(xh), off.data_ptr(), ldoff, col.data_ptr(), N, H, W, Cc, stride, 1, 1,
+                                     L.stream_ptr()), "mi_deform_im2col")
+    return col
+
+
+def _deform_geom(x_shape, w_shape, stride):
+    """the 1x1 convolution over the sampled columns: [N, 9 * C, Ho, Wo] -> [N, Cout, Ho, Wo]"""
+    N, Cin, H, W = x_shape
+    Cout, cw, kh, kw = w_shape
+    if (cw, kh, kw) != (Cin, 3, 3) or stride not in (1, 2) or Cin % 32 or Cout % 32:
+        raise L.MI355Error(f"DeformConv: weight {tuple(w_shape)} on {Cin} channels, stride {stride} (served: 3x3, stride 1 or 2, "
+                           "padding 1, dilation 1, one group, channel counts in multiples of 32)")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return _ConvGeom((N, 9 * Cin, Ho, Wo), (Cout, 9 * Cin, 1, 1), 1, 0)
+
+
+def _tap_major(weight):
+    """[Cout, C, 3, 3] -> [Cout, 9 * C, 1, 1] in the columns' order (tap-major, channels inside a tap)"""
+    return weight.detach().permute(0, 2, 3, 1).reshape(weight.shape[0], -1, 1, 1)
+
+
+class _DeformConvFn(torch.autograd.Function):
+    """DeformConv + FrozenBatchNorm2d (+ ReLU) as one autograd node over (x, offset, weight): sampled im2col, then the
+    1x1 route of the convolution kernels with the folded scale / shift / ReLU in its epilogue (as _FoldedConvFn).
+    Backward: dcol = 1x1 data gradient, gW = weight gradient on (col, dy) permuted back to OIHW, mi_deform_col2im for
+    d_offset and the fp32 dx sum, one pass to bf16 dx that also applies the input's ReLU mask (x_is_relu)."""
+
+    @staticmethod
+    def forward(ctx, x, offset, weight, scale, shift, stride, relu, x_is_relu):
+        g = _deform_geom(x.shape, weight.shape, stride)
+        xh = _nhwc_v(x)
+        off, ldoff = _offset_operand(offset, g.N, g.H, g.W)
+        col = _deform_cols(xh, off, ldoff, g.H, g.W, stride)
+        wf, wd = g.pack(_tap_major(weight), dgrad=True, scale=scale)
+        y = torch.empty(g.N, g.Ho, g.Wo, g.CoutP, dtype=torch.bfloat16, device=x.device)
+        g.fwd(col, wf, y, bias=shift, relu=relu)
+        ctx.g, ctx.relu, ctx.stride, ctx.ldoff, ctx.x_is_relu = g, relu, stride, ldoff, x_is_relu
+        ctx.save_for_backward(xh, off, wd, scale, y if relu else None, col if _DEFORM_KEEP_COL() else None)
+        return _nchw(y, g.Cout)
+
+    @staticmethod
+    def backward(ctx, grad):
+        xh, off, wd, scale, y, col = ctx.saved_tensors
+        g, stride = ctx.g, ctx.stride
+        N, H, W, Cc = xh.shape
+        lib, sp = L.lib(), L.stream_ptr()
+        dyh = _nhwc(grad)
+        if ctx.relu:
+            dyh = _relu_mask(dyh, y)
+        if col is None:
+            col = _deform_cols(xh, off, ctx.ldoff, g.H, g.W, stride)
+        gw = None
+        if ctx.needs_input_grad[2]:
+            gw9 = g.wgrad_scaled(col, dyh, scale)
+            gw = gw9.view(g.Cout, 3, 3, Cc).permute(0, 3, 1, 2).contiguous()
+        dx = doff = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dcol = torch.empty_like(col)
+            g.dgrad(dyh, wd, dcol)
+            # (zeroed by a kernel: a memset node in a captured step serialises the graph's branches,
+            #  profiles/r04_graph_memset_finding.txt)
+            # the fp32 sum and, behind it, max |dcol|: col2im rounds its addends to a grid derived from that maximum, so that
+            # the float atomics give the same bits in any order (a bf16 backward pass amplifies one differing bit to its
+            # rounding-noise floor within a few layers: eager and captured steps would part ways, DESIGN.md 3.11)
+            n32 = N * H * W * Cc
+            buf = torch.empty(n32 + 4, dtype=torch.float32, device=xh.device)
+            dx32, gmax = buf[:n32], buf[n32:]
+            L.check(lib.mi_deform_zero_f32(buf.data_ptr(), buf.numel(), sp), "mi_deform_zero_f32")
+            L.check(lib.mi_deform_absmax(dcol.data_ptr(), dcol.numel(), gmax.data_ptr(), sp), "mi_deform_absmax")
+            doffh = torch.empty(N, g.H, g.W, 32, dtype=torch.bfloat16, device=xh.device)
+            L.check(lib.mi_deform_col2im(dcol.data_ptr(), xh.data_ptr(), _ld(xh), off.data_ptr(), ctx.ldoff, dx32.data_ptr(),
+                                         doffh.data_ptr(), gmax.data_ptr(), N, H, W, Cc, stride, 1, 1, sp), "mi_deform_col2im")
+            if ctx.needs_input_grad[1]:
+                doff = _nchw(doffh, 18)
+            if ctx.needs_input_grad[0]:
+                dxh = torch.empty(N, H, W, Cc, dtype=torch.bfloat16, device=xh.device)
+                mask = xh if ctx.x_is_relu else None
+                L.check(lib.mi_deform_dx_finish(dx32.data_ptr(), L.ptr(mask), _ld(xh) if mask is not None else 0, dxh.data_ptr(), Cc,
+                                                N * H * W, Cc, sp), "mi_deform_dx_finish")
+                dx = dxh.permute(0, 3, 1, 2)
+        return dx, doff, gw, None, None, None, None, None
+
+
+class DeformConv(nn.Module):
+    """detectron2.layers.DeformConv(cin, cout, 3, stride, padding=1, bias=False, norm=FrozenBatchNorm2d): unmodulated, one
+    deformable group, groups 1.  forward(x, offset): offset [N, 18, Ho, Wo], channel 2t / 2t + 1 = row / column offset of tap
+    t = i * 3 + j.  The operator is csrc/deform_conv.hip."""
+
+    def __init__(self, cin, cout, stride=1):
         super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
+        nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")      # c2_msra_fill (DeformBottleneckBlock)
+        self.norm = FrozenBatchNorm2d(cout)
+        self.stride, self.padding = stride, 1
+
+    def forward(self, x, offset, relu=False, x_is_relu=False):
+        """relu: the ReLU that follows runs in the GEMM's epilogue.  x_is_relu: x is a ReLU output - its mask is applied to
+        the data gradient in the pass that rounds it to bf16 (x's producer may mask again - the block's conv1 does, its
+        output also feeds conv2_offset and autograd sums the two gradients into a new tensor; the mask is idempotent)"""
+        if not x.is_cuda:
+            raise L.MI355Error("DeformConv: the MI355X path needs device tensors (no CPU fallback)")
+        scale, shift = self.norm.affine()
+        weight = self.weight
+        grad_on = torch.is_grad_enabled() and (weight.requires_grad or x.requires_grad or offset.requires_grad)
+        if grad_on:
+            return _DeformConvFn.apply(x, offset, weight, scale, shift, self.stride, relu, x_is_relu)
+        # no autograd (evaluation, a frozen stage): nothing saved; a frozen layer's packed image is a constant (Conv2d.forward)
+        with torch.no_grad():
+            g = _deform_geom(x.shape, weight.shape, self.stride)
+            if weight.requires_grad:
+                wf = g.pack(_tap_major(weight), dgrad=False, scale=scale)[0]
+            else:
+                key = (weight.data_ptr(), weight._version, self.norm.__dict__["_affine"][0])
+                c = self.__dict__.get("_image")
+                if c is None or c[0] != key:
+                    c = self.__dict__["_image"] = (key, _same_address(c, g.pack(_tap_major(weight), dgrad=False, scale=scale)[0]))
+                wf = c[1]
+            xh = _nhwc_v(x)
+            off, ldoff = _offset_operand(offset, g.N, g.H, g.W)
+            col = _deform_cols(xh, off, ldoff, g.H, g.W, self.stride)
+            y = torch.empty(g.N, g.Ho, g.Wo, g.CoutP, dtype=torch.bfloat16, device=x.device)
+            g.fwd(col, wf, y, bias=shift, relu=relu)
+            return _nchw(y, g.Cout)
+
+
+class DeformBottleneckBlock(nn.Module):
+    """detectron2 resnet.py DeformBottleneckBlock (deform_modulated False, one deformable group): conv1 1x1 + ReLU,
+    conv2_offset = plain 3x3 convolution with bias and no norm (18 outputs, the 3x3's stride, zero-initialised), conv2 =
+    DeformConv + norm + ReLU, conv3 1x1 + shortcut + ReLU.  Every convolution is its own autograd node."""
+
+    def __init__(self, cin, cout, bottleneck_channels, stride=1, stride_in_1x1=False):
+        super().__init__()
+        self.shortcut = Conv2d(cin, cout, 1, stride=stride) if cin != cout else None
+        s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)
+        self.conv1 = Conv2d(cin, bottleneck_channels, 1, stride=s1)
+        self.conv2_offset = nn.Conv2d(bottleneck_channels, 18, 3, stride=s3, padding=1)
+        self.conv2 = DeformConv(bottleneck_channels, bottleneck_channels, stride=s3)
+        self.conv3 = Conv2d(bottleneck_channels, cout, 1)
+        nn.init.constant_(self.conv2_offset.weight, 0)
+        nn.init.constant_(self.conv2_offset.bias, 0)
+        self.stride = stride
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise L.MI355Error("DeformBottleneckBlock: the MI355X path needs device tensors (no CPU fallback)")
+        out = self.conv1(x, relu=True)
+        po = self.conv2_offset
+        offset = torch.ops.mi355.conv2d(out, po.weight, po.bias, po.stride[0], 1)
+        out = self.conv2(out, offset, relu=True, x_is_relu=True)
+        sc = self.shortcut(x) if self.shortcut is not None else x
+        no_grad_path = not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+        if no_grad_path and _EPI_FUSE() and _FOLDED_FN():
+            return self.conv3(out, add_relu=sc)
+        return _add_relu(self.conv3(out), sc)
+
+
+class ResNet(Backbone):
+    def __init__(self, depth=50, out_features=("res5",), freeze_at=2, stride_in_1x1=False, deform_on_per_stage=(False,) * 4):
+        """deform_on_per_stage (res2 .. res5): every block of a true stage is a DeformBottleneckBlock (d2's make_stage)"""
+        super().__init__()
+        if len(deform_on_per_stage) != 4:
+            raise ValueError(f"ResNet: deform_on_per_stage {deform_on_per_stage} must have one entry per stage res2 .. res5")
         blocks = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}[depth]
         self.stem = BasicStem(3, 64)
         self._out_features = list(out_features)
@@ -577,8 +759,9 @@ class ResNet(Backbone):
         for i, nb in enumerate(blocks):
             name = f"res{i + 2}"
             first = 1 if i == 0 else 2
-            stage = nn.Sequential(*[BottleneckBlock(cin if k == 0 else cout, cout, bc, stride=first if k == 0 else 1,
-                                                    stride_in_1x1=stride_in_1x1) for k in range(nb)])
+            block = DeformBottleneckBlock if deform_on_per_stage[i] else BottleneckBlock
+            stage = nn.Sequential(*[block(cin if k == 0 else cout, cout, bc, stride=first if k == 0 else 1,
+                                          stride_in_1x1=stride_in_1x1) for k in range(nb)])
             for blk in stage:
                 blk.input_is_relu = True    # every block's input is a ReLU output (the stem's max-pooled ReLU, the previous block)
             self.add_module(name, stage)
@@ -630,5 +813,13 @@ def build_resnet_backbone(cfg, input_shape=None):
     r = cfg.MODEL.RESNETS
     if r.NORM != "FrozenBN":
         raise NotImplementedError("build_resnet_backbone: MODEL.RESNETS.NORM FrozenBN (the reference's DETR / SparseInst configs)")
+    deform = [bool(d) for d in r.get("DEFORM_ON_PER_STAGE", [False] * 4)]
+    if any(deform):
+        if r.get("DEFORM_MODULATED", False):
+            raise NotImplementedError("build_resnet_backbone: MODEL.RESNETS.DEFORM_MODULATED True (the modulated form is not "
+                                      "served: csrc/deform_conv.hip is detectron2's unmodulated DeformConv)")
+        if r.get("DEFORM_NUM_GROUPS", 1) != 1:
+            raise NotImplementedError(f"build_resnet_backbone: MODEL.RESNETS.DEFORM_NUM_GROUPS {r.get('DEFORM_NUM_GROUPS')} "
+                                      "(served: one deformable group)")
     return ResNet(depth=r.DEPTH, out_features=r.OUT_FEATURES, freeze_at=cfg.MODEL.BACKBONE.FREEZE_AT,
-                  stride_in_1x1=r.STRIDE_IN_1X1)
+                  stride_in_1x1=r.STRIDE_IN_1X1, deform_on_per_stage=deform)
