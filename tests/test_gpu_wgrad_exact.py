@@ -1,6 +1,7 @@
 """GPU (-m gpu): the convolution weight-gradient kernels (csrc/conv_wgrad.hip) against the plain float64 reference of
 tests/wgrad_ref.py with NO tolerance, through the C ABI (mi_conv2d_wgrad_plan / mi_conv2d_wgrad / mi_conv2d_wgrad_group_plan /
-_run), in every tile configuration of MI_WG_ALL and every launch form.
+_run), in every tile configuration of MI_WG_ALL and every launch form: single, one grid per configuration, the mixed grid
+of the 1x1 layers.
 
 The method: the bf16 operands hold small integers (wgrad_ref.make_operands), so every product is exact in fp32 and every
 partial sum is an integer below 2^24 whatever the order of summation: the result does not depend on the split-K layout, the
@@ -16,10 +17,6 @@ as a sum; the operand buffers are NaN outside the descriptor's views."""
 import collections
 import ctypes as C
 import functools
-import json
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -34,7 +31,6 @@ DEV = "cuda"
 MI_EINVAL = -1                 # include/mi355_det.h
 SENT = -1234.5                 # guard words around a gradient
 GW_GUARD, WS_GUARD = 64, 256   # floats / bytes
-COUNT = collections.Counter()  # launches made by run_single / run_group (the child process reports them)
 
 # MI_WG_ALL of csrc/conv_wgrad.hip, written out: (NT, MI, NJ, WCO, WCI, TP) - 28 instantiations
 WG_ALL = ({(9, 4, 1, 1, 4, tp) for tp in (64, 128)} | {(9, 2, 1, 2, 2, tp) for tp in (64, 128)} |
@@ -187,7 +183,6 @@ def run_single(job, label, runs=1):
     d.ws, d.ws_bytes = ws.data_ptr(), need
     for _ in range(runs):
         L.check(lib.mi_conv2d_wgrad(C.byref(d), L.stream_ptr()), "mi_conv2d_wgrad %s" % (label,))
-        COUNT["single"] += 1
     torch.cuda.synchronize()
     bad = job.problems(label, runs)
     if not bool((ws[need:] == 0xFF).all()):
@@ -196,7 +191,7 @@ def run_single(job, label, runs=1):
 
 
 def run_group(jobs, labels, runs=1):
-    """mi_conv2d_wgrad_group_plan / _run (the switches are read from the environment per plan); returns (problems, meta)"""
+    """mi_conv2d_wgrad_group_plan / _run (MI_WG_MULTI is read from the environment per plan); returns (problems, meta)"""
     lib = L.lib()
     descs = (L.mi_wgrad_desc * len(jobs))()
     for d, j in zip(descs, jobs):
@@ -212,7 +207,6 @@ def run_group(jobs, labels, runs=1):
     bad = []
     for r in range(runs):
         L.check(lib.mi_conv2d_wgrad_group_run(C.byref(meta), table.data_ptr(), L.stream_ptr()), "group run")
-        COUNT["group jobs"] += len(jobs)
         torch.cuda.synchronize()
         for j, lab in zip(jobs, labels):
             bad += j.problems((lab, "run %d" % r), r + 1)
@@ -272,16 +266,8 @@ def matrix_b_jobs(**kw):
     return jobs, labels
 
 
-def run_matrix_b_single():
-    bad = []
-    for j, lab in zip(*matrix_b_jobs()):
-        bad += run_single(j, lab)
-    return bad
-
-
 def test_every_instantiation_single_launch(monkeypatch):
     monkeypatch.setenv("MI_WG_MULTI", "0")
-    monkeypatch.setenv("MI_WG_FIXUP", "0")
     seen = set()
     for j, lab in zip(*matrix_b_jobs()):      # coverage is asserted, not assumed: the configuration the launcher picks
         meta = L.mi_wgrad_group()
@@ -291,7 +277,9 @@ def test_every_instantiation_single_launch(monkeypatch):
         assert meta.ngroups == 1, lab
         seen.add(tuple(meta.g[0].cfg))
     assert seen == WG_ALL, (sorted(WG_ALL - seen), sorted(seen - WG_ALL))
-    bad = run_matrix_b_single()
+    bad = []
+    for j, lab in zip(*matrix_b_jobs()):
+        bad += run_single(j, lab)
     assert not bad, bad
 
 
@@ -318,7 +306,7 @@ def _geo_specs(cls):
 
 
 @pytest.mark.parametrize("cls", list(GEO_CLASSES))
-def test_geometry_tiles_splits_ring_and_block_order(monkeypatch, cls):
+def test_geometry_tiles_splits_ring_and_block_order(cls):
     bad = []
     for s in _geo_specs(cls):
         nt = ntiles_of(s)
@@ -333,24 +321,20 @@ def test_geometry_tiles_splits_ring_and_block_order(monkeypatch, cls):
             assert ntiles_of(s, TH=th, TW=tw) == s.N * (-(-s.oH // th)) * (-(-s.oW // tw)), (cls, s.H, s.W, th, tw)
         for k in (1, 2, 3, 7, nt, nt + 5):
             assert split_count(s, splitk=k) == -(-nt // -(-nt // min(k, nt))), (cls, s.H, s.W, k)
-        for xmap in ("0", "1", "2"):
-            monkeypatch.setenv("MI_WG_XMAP", xmap)
-            for kw in (dict(), dict(splitk=3), dict(splitk=12), dict(splitk=nt, cfg_tp=128)):
-                bad += run_single(Job(s, **kw), (cls, s.H, s.W, kw, "xmap " + xmap))
-        monkeypatch.delenv("MI_WG_XMAP")
+        # the block order (wg_decode): no full group of 8 splits, one full group plus a remainder of 4, one tile per split
+        for kw in (dict(), dict(splitk=3), dict(splitk=12), dict(splitk=nt, cfg_tp=128)):
+            bad += run_single(Job(s, **kw), (cls, s.H, s.W, kw, "block order"))
     assert not bad, bad[:20]
 
 
-def test_block_order_rectangle_path(monkeypatch):
-    """MI_WG_XMAP=2 with 12 splits on layers of 2 x 2 (cout, cin) tiles: 8 splits in whole groups, the other r = 4 with
-    r * pairs % 8 == 0 take the rectangle decode of wg_decode; the other orders on the same layers"""
+def test_block_order_groups_of_eight_plus_remainder():
+    """12 splits on layers of 2 x 2 (cout, cin) tiles: 8 splits in whole groups of 8 block ids, the other r = 4 dealt pair by
+    pair (the remainder decode of wg_decode)"""
     bad = []
     for s in (spec(3, 1, 128, 128, 3, 16, 32, seed=200), spec(3, 2, 64, 128, 3, 32, 64, seed=201)):
         for tp, splitk in ((64, 12), (128, 12)):
             assert split_count(s, splitk=splitk, cfg_tp=tp) == 12, (s, tp)
-            for xmap in ("2", "0", "1"):
-                monkeypatch.setenv("MI_WG_XMAP", xmap)
-                bad += run_single(Job(s, splitk=splitk, cfg_tp=tp), (s.stride, tp, "xmap " + xmap))
+            bad += run_single(Job(s, splitk=splitk, cfg_tp=tp), (s.stride, tp))
     assert not bad, bad
 
 
@@ -404,19 +388,17 @@ def _iam_guards_ok(gwall):
     return bool(torch.all(h[:GW_GUARD] == SENT) and torch.all(h[-GW_GUARD:] == SENT))
 
 
-def test_grouped_iam_convolution_layout(monkeypatch):
-    """single launches per group, then the G jobs as one grouped launch (how WgradBatch flushes them), both fix-up settings"""
+def test_grouped_iam_convolution_layout():
+    """single launches per group, then the G jobs as one grouped launch (how WgradBatch flushes them)"""
     jobs, gwall = _iam_jobs()
     bad = []
     for g, j in enumerate(jobs):
         bad += run_single(j, ("iam single", g))
     assert _iam_guards_ok(gwall)
-    for fix in ("0", "1"):
-        monkeypatch.setenv("MI_WG_FIXUP", fix)
-        jobs, gwall = _iam_jobs()
-        b, _ = run_group(jobs, [("iam group", g, "fixup " + fix) for g in range(len(jobs))], runs=2)
-        bad += b
-        assert _iam_guards_ok(gwall)
+    jobs, gwall = _iam_jobs()
+    b, _ = run_group(jobs, [("iam group", g) for g in range(len(jobs))], runs=2)
+    bad += b
+    assert _iam_guards_ok(gwall)
     assert not bad, bad
 
 
@@ -480,38 +462,29 @@ def _group_jobs():
     return jobs, labels
 
 
-@pytest.mark.parametrize("fixup", ["0", "1"])
-@pytest.mark.parametrize("multi", ["0", "3", "4"])
-def test_grouped_launch_forms(monkeypatch, multi, fixup):
-    """one grid per tile configuration, the mixed grids (MI_WG_MULTI 3: the 1x1 layers, 4: the 3x3 layers too) and the
-    fix-up form, two runs of the same table: every result equals the reference, not merely the other form"""
+@pytest.mark.parametrize("multi", ["0", "3"])
+def test_grouped_launch_forms(monkeypatch, multi):
+    """one grid per tile configuration and the mixed grid of the 1x1 layers (MI_WG_MULTI 3), two runs of the same table:
+    every result equals the reference, not merely the other form"""
     monkeypatch.setenv("MI_WG_MULTI", multi)
-    monkeypatch.setenv("MI_WG_FIXUP", fixup)
     jobs, labels = _group_jobs()
     assert ntiles_of(_geo_specs("1x1")[2]) == 3          # (the 5 x 3 map: one tile per image)
     bad, meta = run_group(jobs, labels, runs=2)
     cfgs = group_cfgs(meta)
-    assert all(meta.g[i].fixup == int(fixup) for i in range(meta.ngroups))
-    if fixup == "1":
-        assert meta.red_blocks == 0 and meta.red9_blocks == 0
-    if multi == "0" or fixup == "1":                     # (the fix-up form keeps one grid per configuration)
+    if multi == "0":
         assert set(cfgs) == WG_ALL and len(cfgs) == 28
     else:
         assert {c for c in cfgs if c[0] == 1} == {(1, 0, 0, 2, 2, 64), (1, 0, 0, 2, 2, 128)}
-        assert (any(c[0] == 9 and c[1] == 0 for c in cfgs)) == (multi == "4")
+        assert not any(c[0] == 9 and c[1] == 0 for c in cfgs)
     assert not bad, bad[:20]
 
 
 def test_group_of_one_job_and_group_with_bias_gradients(monkeypatch):
-    monkeypatch.setenv("MI_WG_FIXUP", "0")
     bad = []
     for s in (EPI_SPECS[0], EPI_SPECS[2]):
-        for fix in ("0", "1"):
-            monkeypatch.setenv("MI_WG_FIXUP", fix)
-            b, meta = run_group([Job(s)], [("one job", len(s.taps), "fixup " + fix)], runs=2)
-            assert meta.ngroups == 1
-            bad += b
-    monkeypatch.setenv("MI_WG_FIXUP", "0")
+        b, meta = run_group([Job(s)], [("one job", len(s.taps))], runs=2)
+        assert meta.ngroups == 1
+        bad += b
     for multi in ("0", "3"):
         monkeypatch.setenv("MI_WG_MULTI", multi)
         jobs = [Job(s, gbias=(i != 1), **kw) for i, (s, kw) in enumerate(zip(EPI_SPECS, (dict(), dict(), dict(cfg_tp=128), dict(splitk=3), dict(scaled=True))))]
@@ -520,10 +493,10 @@ def test_group_of_one_job_and_group_with_bias_gradients(monkeypatch):
     assert not bad, bad
 
 
-# ------------------------------------------------------------------------------- (g) the switches read once per process
-def run_child_extras():
-    """beyond matrix (b), for the process-wide switches: the other LDS layout meets ragged, tiny and single-row maps with
-    tile / split / ring overrides, and the other reduce kernels meet the epilogues"""
+# --------------------------------------------------------------------------- (g) overrides on the awkward maps, epilogues
+def test_overrides_on_ragged_tiny_and_single_row_maps_and_epilogues():
+    """beyond matrix (b): ragged, tiny and single-row maps with tile / split / ring overrides in both pixel-tile sizes, and the
+    epilogue combinations of the split-K reduction"""
     bad = []
     for cls in GEO_CLASSES:
         sp = _geo_specs(cls)
@@ -536,28 +509,7 @@ def run_child_extras():
     for s in EPI_SPECS:
         for kw in (dict(accumulate=1, scaled=True), dict(accumulate=1, splitk=5), dict(scaled=True, cfg_tp=128), dict(gbias=True, scaled=True)):
             bad += run_single(Job(s, **kw), ("epilogue", len(s.taps), s.stride, s.Cin, kw), runs=2 if kw.get("accumulate") else 1)
-    return bad
-
-
-CHILD_ENVS = [dict(MI_WG_V3="0", MI_WG_RED9="1", MI_WG_REDSL="1"), dict(MI_WG_V3="2", MI_WG_REDSL="16"), dict(MI_WG_REDSL="8")]
-
-
-def test_switches_read_once_per_process():
-    """MI_WG_V3 (the other LDS layout for each tap class), MI_WG_RED9 (the 3x3 reduce kernel) and MI_WG_REDSL (split lanes
-    of the reduction): matrix (b), single and grouped (reduce grid and fix-up), and run_child_extras in a fresh process per setting (tests/wgrad_exact_gpu_child.py).  A
-    child that ends abnormally ends the test: nothing further is started on the GPU."""
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "wgrad_exact_gpu_child.py")
-    for env in CHILD_ENVS:
-        e = {k: v for k, v in os.environ.items() if not k.startswith("MI_WG_")}
-        e.update(env)
-        r = subprocess.run([sys.executable, child], capture_output=True, text=True, timeout=120, env=e)
-        assert r.returncode == 0, (env, r.returncode, (r.stdout + r.stderr)[-2000:])
-        res = json.loads(r.stdout.strip().splitlines()[-1])
-        nb = 2 * len(matrix_b())
-        assert res["env"] == env and res["single"] >= nb + 100 and res["group_jobs"] == 4 * nb, res     # (two forms x two runs)
-        assert res["cfgs"] == sorted(list(c) for c in WG_ALL), res["cfgs"]
-        assert res["fixup_groups"] == 28 and (res["red9_blocks"] > 0) == (env.get("MI_WG_RED9") == "1"), res
-        assert res["bad"] == [], (env, res["bad"][:10])
+    assert not bad, bad[:20]
 
 
 # --------------------------------------------------------------------------------------------------- (h) the check has teeth
