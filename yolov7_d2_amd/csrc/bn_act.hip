@@ -25,6 +25,8 @@
 #define BN_MAXC 2048
 // accumulator layout: [slot][CA][2] with CA = C rounded up to 32 - the CoutPad the conv epilogue adds its tile sums with
 #define BN_ACC_C(C) (((C) + 31) / 32 * 32)
+// every tensor access is a 16-byte vector: NULL (an absent optional tensor) passes
+static inline bool bn_al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
 // ------------------------------------------------------------------ eval-mode affine
 __global__ void bn_eval_affine_kernel(const float* gamma, const float* beta, const float* rm, const float* rv,
@@ -324,6 +326,7 @@ extern "C" int mi_bn_act_bwd_reduce(const void* da, int ldda, const void* y, int
   MI_REQUIRE(da && y && scale && shift && mean && invstd && dacc, "bn_bwd_reduce: null");
   MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_bwd_reduce: C %d (need C %% 8 == 0, C <= %d)", C, BN_MAXC);
   MI_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && nblk > 0, "bn_bwd_reduce: ld");
+  MI_REQUIRE(bn_al16(da) && bn_al16(y), "bn_bwd_reduce: align");
   BnRedK k;
   k.da = (const __bf16*)da; k.y = (const __bf16*)y; k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd;
   k.dacc = dacc; k.ldda = ldda; k.ldy = ldy; k.nslots = nslots; k.C8 = C / 8; k.npix = npix;
@@ -461,6 +464,7 @@ extern "C" int mi_bn_act_bwd_apply(const void* da, int ldda, const void* y, int 
   MI_REQUIRE(da && y && scale && shift && mean && invstd && gamma && dacc && dy && count > 0, "bn_bwd_apply: null");
   MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_bwd_apply: C %d", C);
   MI_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && (!dres || lddres % 8 == 0), "bn_bwd_apply: ld");
+  MI_REQUIRE(bn_al16(da) && bn_al16(y) && bn_al16(dy) && bn_al16(dres), "bn_bwd_apply: align");
   BnBwdK k;
   k.da = (const __bf16*)da; k.y = (const __bf16*)y; k.dy = (__bf16*)dy; k.dres = (__bf16*)dres; k.dacc = dacc;
   k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd; k.gamma = gamma; k.dgamma = dgamma;
@@ -832,6 +836,7 @@ extern "C" int mi_bn_act_bwd_fused(const void* da, int ldda, const void* y, int 
   MI_REQUIRE(da && y && scale && shift && mean && invstd && gamma && dacc && dy && barrier_words && count > 0, "bn_bwd_fused: null");
   MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_bwd_fused: C %d", C);
   MI_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && (!dres || lddres % 8 == 0), "bn_bwd_fused: ld");
+  MI_REQUIRE(bn_al16(da) && bn_al16(y) && bn_al16(dy) && bn_al16(dres), "bn_bwd_fused: align");
   MI_REQUIRE(bn_fused_fits(npix, ldda, ldy, lddy, dres ? lddres : 0), "bn_bwd_fused: tensors beyond 4 GB (use reduce + apply)");
   BnFusK k;
   k.da = (const __bf16*)da; k.y = (const __bf16*)y; k.dy = (__bf16*)dy; k.dres = (__bf16*)dres; k.dacc = dacc;
@@ -876,6 +881,14 @@ extern "C" int mi_bn_group_plan(int kind, const mi_bn_job* jobs, int n, void* ta
     const int nslots = (b.nslots >= 1 && b.nslots <= MI_BN_SLOTS) ? b.nslots : MI_BN_SLOTS;
     const int64_t total = b.npix * (C / 8);
     int nb = ew_blocks(total);
+    // what the single-layer entry points require of the tensors a kind touches (the others may hold anything)
+    if (kind == 0)
+      MI_REQUIRE(bn_al16(b.y) && bn_al16(b.a) && bn_al16(b.res), "bn_group_plan: job %d align", j);
+    else
+      MI_REQUIRE(b.ldda % 8 == 0 && b.ldy % 8 == 0 && bn_al16(b.da) && bn_al16(b.y), "bn_group_plan: job %d ld / align", j);
+    if (kind >= 2)
+      MI_REQUIRE(b.lddy % 8 == 0 && (!b.dres || b.lddres % 8 == 0) && bn_al16(b.dy) && bn_al16(b.dres),
+                 "bn_group_plan: job %d ld / align", j);
     if (kind == 0) {
       MI_REQUIRE(b.y && b.a && b.scale && b.shift && b.ldy % 8 == 0 && b.lda % 8 == 0 && (!b.res || b.ldres % 8 == 0),
                  "bn_group_plan: fwd job %d", j);
