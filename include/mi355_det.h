@@ -790,6 +790,44 @@ int mi_jpeg_color(const mi_jpeg_job* jobs_dev, int njobs, int total_blocks, mi_s
 int mi_rle_encode(const uint8_t* masks, int n, int H, int W, int max_runs, uint32_t* counts, int32_t* nruns, mi_stream_t s);
 int mi_rle_to_string(const uint32_t* counts, int nruns, char* out, int out_cap);
 
+/* ---- COCO AP / AR evaluation (csrc/coco_eval.hip): cocoapi's COCOeval evaluate -> accumulate and maskApi.c's bbIou / rleIou /
+ * rleDecode / rleFrString, un-vendored and restated; fp64 and integers in the originals' operation order (parity unpinned
+ * against pycocotools itself; tests/cocoeval_ref.py is the restatement the kernels equal element for element).
+ * mi_coco_box_iou: dt [D][4], gt [G][4] XYWH doubles, gcrowd [G] (may be NULL) -> iou [D][G]: 0 unless w > 0 and h > 0 of the
+ *   intersection, else i / (crowd ? da : da + ga - i).
+ * mi_coco_mask_iou: dense masks uint8 [D][H][W], [G][H][W] (non-zero = foreground), any H, W >= 1 -> inter [D][G], darea [D],
+ *   garea [G] (pixel counts) and iou [D][G] = i / u with u = 1 if i == 0, else crowd ? da : da + ga - i.  ws: the bit-packed
+ *   masks, mi_coco_mask_iou_ws_bytes(D, G, H, W) bytes, 8-byte aligned.
+ * mi_rle_decode: counts [n][max_runs], nruns [n] (device; run lengths of the COLUMN-major scan, first a run of zeros) ->
+ *   out [n][H][W] row-major 0 / 1.  cum_ws: [n][max_runs] scratch.  err [n] (device) is set to 1 for a mask whose counts do
+ *   not sum to H * W (or whose nruns is outside [0, max_runs]); that mask is written as zeros.  wait != 0: the call waits
+ *   for the stream, reads err and returns MI_EINVAL for such a mask - the only waiting form; wait == 0 never synchronises.
+ * mi_rle_from_string: host code, the inverse of mi_rle_to_string: NUL-terminated string -> counts; returns the number of
+ *   runs, MI_EINVAL when max_runs is too small.
+ * mi_coco_match: evaluateImg for every (cell = image * K + category, area range); lane = IoU threshold (T <= 64).
+ *   Detections sorted by (cell, -score, stable): det_row [N] (offset of the detection's row in iou), det_area [N], det_start
+ *   [ncell + 1]; the first max_det of a cell enter.  Ground truths sorted by (cell, annotation order): gt_start [ncell + 1],
+ *   gt_col [Gt] (column in the row), gt_area [Gt], gt_crowd [Gt].  area_rng [A][2], bounds inclusive.  Writes dtm / dtig
+ *   [A][T][N] (matched / ignored; zero for detections that did not enter), gtig [A][Gt], npig [ncell][A] (ground truths
+ *   not ignored); gtm [A][T][Gt] is scratch.
+ * mi_coco_accumulate: detections sorted by (category, -score, stable over ascending image, rank): dtm / dtig [A][T][N], score
+ *   [N], rank [N] (place in the image's score order; rank < max_dets[m] enters), cat_start [K + 1], npig [K][A] -> precision
+ *   and scores [T][R][K][A][M], recall [T][K][A][M]; -1 where npig == 0. */
+int mi_coco_box_iou(const double* dt, int D, const double* gt, int G, const uint8_t* gcrowd, double* iou, mi_stream_t s);
+int64_t mi_coco_mask_iou_ws_bytes(int D, int G, int H, int W);
+int mi_coco_mask_iou(const uint8_t* dmasks, int D, const uint8_t* gmasks, int G, int H, int W, const uint8_t* gcrowd, void* ws,
+                     int64_t ws_bytes, int64_t* inter, int64_t* darea, int64_t* garea, double* iou, mi_stream_t s);
+int mi_rle_decode(const uint32_t* counts, const int32_t* nruns, int n, int max_runs, int H, int W, uint32_t* cum_ws, uint8_t* out,
+                  int32_t* err, int wait, mi_stream_t s);
+int mi_rle_from_string(const char* s, uint32_t* counts, int max_runs);
+int mi_coco_match(const double* iou, const int64_t* det_row, const double* det_area, const int64_t* det_start,
+                  const int64_t* gt_start, const int32_t* gt_col, const double* gt_area, const uint8_t* gt_crowd,
+                  const double* iou_thrs, int T, const double* area_rng, int A, int max_det, int64_t ncell, int64_t N, int64_t Gt,
+                  uint8_t* dtm, uint8_t* dtig, uint8_t* gtig, uint8_t* gtm, int32_t* npig, mi_stream_t s);
+int mi_coco_accumulate(const uint8_t* dtm, const uint8_t* dtig, const double* score, const int32_t* rank, const int64_t* cat_start,
+                       const int64_t* npig, const int32_t* max_dets, const double* rec_thrs, int T, int R, int K, int A, int M,
+                       int64_t N, double* precision, double* recall, double* scores, mi_stream_t s);
+
 /* ---- batched NMS -------------------------------------------------------------
  * replaces torchvision.ops.batched_nms as called by postprocess (utils/boxes.py:199).
  * boxes xyxy fp32 [n][4], scores [n], idxs (class id as float, as the reference passes) [n].

@@ -338,6 +338,14 @@ _PROTOS = {
     "mi_jpeg_color": (C.c_int, [_vp, _i, _i, _vp]),
     "mi_rle_encode": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mi_rle_to_string": (C.c_int, [_vp, _i, C.c_char_p, _i]),
+    "mi_coco_box_iou": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "mi_coco_mask_iou_ws_bytes": (C.c_int64, [_i, _i, _i, _i]),
+    "mi_coco_mask_iou": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mi_rle_decode": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "mi_rle_from_string": (C.c_int, [C.c_char_p, _vp, _i]),
+    "mi_coco_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                _vp, _vp]),
+    "mi_coco_accumulate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp]),
     "mi_yolox_onnx_layout": (C.c_int, [_vp, _vp, _i, _i, _i, _vp]),
     "mi_yolox_iou_loss": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mi_pairwise_bbox_iou": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp]),
