@@ -268,6 +268,52 @@ int mi_pack_jobs_layout(mi_pack_job* jobs_host, int njobs);
 /* kk_max: the largest tap count (KK) of the table: sizes the kernel's LDS tile */
 int mi_pack_conv_weights_batch(const mi_pack_job* jobs_dev, int njobs, int total_blocks, int kk_max, mi_stream_t s);
 
+/* ---- grouped 3x3 convolution (csrc/conv_grouped.hip) ---------------------------------
+ * nn.Conv2d(C, C, 3, stride, padding = 1, groups = G) with square groups of Cg = C / G in {8, 16, 24, 32} channels: the 3x3
+ * of a RegNet X / Y block (backbone/regnet.py; group widths 8 / 16 / 24) and of ResNeXt (32).  Served: 3x3, padding 1,
+ * dilation 1, stride 1 or 2, G >= 1; anything else returns MI_EINVAL naming the quantity, before any launch and before any
+ * pointer is looked at.
+ * x and y are bf16 NHWC views with pixel strides ldx, ldy >= C (multiples of 8; base pointers 16-byte aligned): group g owns
+ * channels [g * Cg, (g + 1) * Cg), channels >= C of a pixel are never read and never written.  Ho = (H - 1) / stride + 1.
+ *   forward          y[n][oy][ox][g*Cg+co] = bf16(bias[g*Cg+co] + sum over (r, s, ci) of
+ *                        x[n][oy*stride-1+r][ox*stride-1+s][g*Cg+ci] * w[g*Cg+co][ci][r][s]),  x = 0 outside the map;
+ *                    fp32 accumulation on the matrix cores, fp32 bias (may be NULL), one rounding at the store.
+ *   data gradient    the exact adjoint: reads y (= dy) and the data-gradient image, writes EVERY pixel of x (= dx) itself
+ *                    (no zero fill by the caller, also where a stride-2 layer's taps do not reach).
+ *   weight gradient  gw[g*Cg+co][ci][r][s] fp32 (the parameter's layout [C][Cg][3][3]), overwritten; gbias (may be NULL):
+ *                    fp32 [C] column sums of dy from the same launches.  Split over pixel tiles into a caller-owned
+ *                    workspace, the partials summed in a fixed order by a second launch: no atomics, bit-reproducible.
+ * One launch per pass over all groups (the weight gradient: one + its reduction).
+ * mi_gconv_pack_weight: fp32 [C][Cg][3][3] -> the forward and the data-gradient bf16 image (either may be NULL), each
+ * mi_gconv_weight_image_bytes(C, Cg) bytes, rounded to nearest even as mi_pack_conv_weight does.  An image is the kernels'
+ * MFMA fragment order [G][MT][NK][64 lanes][8] with MT = ceil(Cg / 16), NK = ceil(9 * Cg / 32): entry (g, mt, m, lane, j) has
+ * row = mt*16 + (lane & 15), octet q = 4*m + (lane >> 4), tap t = q / (Cg/8), k = (q % (Cg/8))*8 + j and holds
+ * w[g*Cg+row][k][t/3][t%3] (forward) or w[g*Cg+k][row][2-t/3][2-t%3] (data gradient); zero where row >= Cg or q >= 9*Cg/8. */
+typedef struct mi_gconv_desc {
+  void* x;            /* the layer's input side: x (forward, weight gradient: read) or dx (data gradient: written)  */
+  void* y;            /* the layer's output side: y (forward: written) or dy (both gradients: read)                 */
+  const void* w;      /* packed image: the forward image (forward), the data-gradient image (data gradient)          */
+  const float* bias;  /* forward: fp32 [C] or NULL                                                                    */
+  float* gw;          /* weight gradient: fp32 [C][Cg][3][3]                                                          */
+  float* gbias;       /* weight gradient: fp32 [C] or NULL                                                            */
+  void* ws;           /* weight gradient: workspace, 16-byte aligned                                                  */
+  int64_t ws_bytes;   /* >= mi_gconv_wgrad_plan()                                                                     */
+  int32_t ldx, ldy;
+  int32_t N, H, W;    /* the layer's input map; the output map is Ho x Wo                                             */
+  int32_t Cin, Cout, G;
+  int32_t kh, kw, stride, padding, dilation;
+  int32_t rsv_;
+} mi_gconv_desc;
+int mi_gconv_desc_size(void);   /* sizeof(mi_gconv_desc) as compiled (binding self-check) */
+int64_t mi_gconv_weight_image_bytes(int C, int Cg);
+int mi_gconv_pack_weight(const float* w, int C, int Cg, void* wf, void* wd, mi_stream_t s);
+int mi_gconv_fwd(const mi_gconv_desc* d, mi_stream_t s);
+int mi_gconv_dgrad(const mi_gconv_desc* d, mi_stream_t s);
+/* workspace bytes of mi_gconv_wgrad for this descriptor (pointers may be NULL), or < 0; *nsplit (may be NULL) receives the
+ * number of split partials: the bytes are nsplit * (C * Cg * 9 + C) * 4 */
+int64_t mi_gconv_wgrad_plan(const mi_gconv_desc* d, int32_t* nsplit);
+int mi_gconv_wgrad(const mi_gconv_desc* d, mi_stream_t s);
+
 /* ---- depthwise 3x3 convolution ------------------------------------------------
  * the `dconv` of DWConv (backbone/layers/wrappers.py:86-102: BaseConv(C, C, ksize, stride, groups=C); the reference
  * builds it with ksize 3 everywhere, darknetx.py:113-160): NHWC bf16, pad 1, stride 1 or 2, C % 8 == 0.

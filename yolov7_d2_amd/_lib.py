@@ -108,6 +108,14 @@ class mi_wgrad_desc(C.Structure):
     ]
 
 
+class mi_gconv_desc(C.Structure):
+    """grouped 3x3 convolution (csrc/conv_grouped.hip): one record for the forward, the data gradient and the weight gradient"""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("gw", C.c_void_p),
+                ("gbias", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("ldx", "ldy", "N", "H", "W", "Cin", "Cout", "G", "kh", "kw", "stride", "padding",
+                                         "dilation", "rsv_")]
+
+
 class mi_yolox_loss_desc(C.Structure):
     _fields_ = [
         ("preds", C.c_void_p), ("labels", C.c_void_p), ("anchors", C.c_void_p),
@@ -268,6 +276,13 @@ _PROTOS = {
     "mi_deform_absmax": (C.c_int, [_vp, _i64, _vp, _vp]),
     "mi_deform_zero_f32": (C.c_int, [_vp, _i64, _vp]),
     "mi_deform_dx_finish": (C.c_int, [_vp, _vp, _i, _vp, _i, _i64, _i, _vp]),
+    "mi_gconv_desc_size": (C.c_int, []),
+    "mi_gconv_weight_image_bytes": (C.c_int64, [_i, _i]),
+    "mi_gconv_pack_weight": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp]),
+    "mi_gconv_fwd": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
+    "mi_gconv_dgrad": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
+    "mi_gconv_wgrad_plan": (C.c_int64, [C.POINTER(mi_gconv_desc), C.POINTER(C.c_int32)]),
+    "mi_gconv_wgrad": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
     "mi_upsample2x_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "mi_upsample2x_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mi_spp_pool_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

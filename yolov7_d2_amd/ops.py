@@ -5,6 +5,8 @@ The whole-step plan (plan.py) is the fast path; these ops expose the SAME kernel
 for a model that keeps the reference's own nn.Module tree and swaps single operators:
 
     torch.ops.mi355.conv2d(x, weight, bias, stride, padding)                -> nn.Conv2d (1x1 / 3x3, stride 1 / 2)
+    torch.ops.mi355.conv2d_grouped(x, weight, bias, stride, padding, groups) -> nn.Conv2d (3x3, padding 1, stride 1 / 2, square
+                                                                               groups of 8 / 16 / 24 / 32 channels: RegNet, ResNeXt)
     torch.ops.mi355.conv_bn_silu(x, weight, gamma, beta, running_mean, running_var, stride, eps, training)
                                                                             -> BaseConv.forward (wrappers.py:60-83)
     torch.ops.mi355.batched_nms(boxes, scores, idxs, iou_threshold)         -> torchvision.ops.batched_nms (boxes.py:199)
@@ -14,7 +16,8 @@ for a model that keeps the reference's own nn.Module tree and swaps single opera
 
 `patch_base_convs(module)` re-points the forward of every BaseConv-shaped sub-module (children `conv`: bias-free
 nn.Conv2d, `bn`: nn.BatchNorm2d, `act`: nn.SiLU - the reference's own class qualifies unmodified) to
-torch.ops.mi355.conv_bn_silu on its own parameters.
+torch.ops.mi355.conv_bn_silu on its own parameters.  `patch_grouped_convs(module)` does the same for every grouped 3x3
+nn.Conv2d that torch.ops.mi355.conv2d_grouped serves.
 
 Tensors: activations NCHW bf16 in channels_last memory (= the kernels' NHWC; anything else is converted on entry),
 weights / BatchNorm parameters fp32 as nn.Conv2d / nn.BatchNorm2d hold them.  HIP device tensors only: there is no CPU
@@ -735,6 +738,105 @@ def _pad_last(t, CP):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ mi355::conv2d_grouped
+# nn.Conv2d(C, C, 3, stride, padding=1, groups=G) with square groups of Cg = C / G in GCONV_WIDTHS channels on the grouped
+# kernels (csrc/conv_grouped.hip): one launch per pass over all groups; everything else is refused by the library, by name
+GCONV_WIDTHS = (8, 16, 24, 32)
+_LIBDEF.define("conv2d_grouped(Tensor x, Tensor weight, Tensor? bias, int stride, int padding, int groups) -> Tensor")
+_LIBDEF.define("conv2d_grouped_backward(Tensor grad, Tensor x, Tensor weight, bool need_dx, bool need_gw, bool need_gb, "
+               "int stride, int padding, int groups) -> (Tensor, Tensor, Tensor)")
+
+
+def _gconv_desc(x_shape, w_shape, stride, padding, groups):
+    N, Cin, H, W = x_shape
+    Cout, cg, kh, kw = w_shape
+    if groups < 1 or Cin % groups or cg != Cin // groups:
+        raise L.MI355Error(f"mi355 conv2d_grouped: weight {tuple(w_shape)} does not fit input channels {Cin} in {groups} groups")
+    d = L.mi_gconv_desc()
+    d.N, d.H, d.W, d.Cin, d.Cout, d.G = N, H, W, Cin, Cout, groups
+    d.kh, d.kw, d.stride, d.padding, d.dilation = kh, kw, stride, padding, 1
+    return d
+
+
+def _gconv_images(weight, C, Cg, fwd, dgrad):
+    """(forward image, data-gradient image) of the [C][Cg][3][3] parameter; an image that is not asked for is None"""
+    n = L.check(L.lib().mi_gconv_weight_image_bytes(C, Cg), "mi_gconv_weight_image_bytes") // 2
+    w32 = weight.detach().float().contiguous()
+    wf = torch.empty(n, dtype=torch.bfloat16, device=weight.device) if fwd else None
+    wd = torch.empty(n, dtype=torch.bfloat16, device=weight.device) if dgrad else None
+    L.check(L.lib().mi_gconv_pack_weight(w32.data_ptr(), C, Cg, L.ptr(wf), L.ptr(wd), L.stream_ptr()), "mi_gconv_pack_weight")
+    return wf, wd
+
+
+def _gconv_out(H, W, stride):
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def _conv2d_grouped_cuda(x, weight, bias, stride, padding, groups):
+    d = _gconv_desc(x.shape, weight.shape, stride, padding, groups)
+    # (a refusal needs no tensor: the library names the unserved quantity before it looks at a pointer)
+    L.check(L.lib().mi_gconv_wgrad_plan(C.byref(d), None), "mi355 conv2d_grouped")
+    N, Cc, H, W = x.shape
+    Ho, Wo = _gconv_out(H, W, stride)
+    xh = _nhwc_v(x)
+    wf, _ = _gconv_images(weight, Cc, Cc // groups, True, False)
+    b32 = None if bias is None else bias.detach().float().contiguous()
+    y = torch.empty(N, Ho, Wo, Cc, dtype=torch.bfloat16, device=x.device)
+    d.x, d.ldx, d.y, d.ldy, d.w, d.bias = xh.data_ptr(), _ld(xh), y.data_ptr(), Cc, wf.data_ptr(), L.ptr(b32)
+    L.check(L.lib().mi_gconv_fwd(C.byref(d), L.stream_ptr()), "mi_gconv_fwd")
+    return _nchw(y, Cc)
+
+
+def _conv2d_grouped_backward_cuda(grad, x, weight, need_dx, need_gw, need_gb, stride, padding, groups):
+    """each gradient only when asked for (an empty tensor otherwise); the bias gradient leaves with the weight-gradient
+    launches, the weight gradient comes back in the parameter's layout [C][Cg][3][3]"""
+    d = _gconv_desc(x.shape, weight.shape, stride, padding, groups)
+    N, Cc, H, W = x.shape
+    dyh = _nhwc_v(grad)
+    d.y, d.ldy = dyh.data_ptr(), _ld(dyh)
+    none = torch.zeros(0, device=x.device)
+    dx = gw = gb = none
+    if need_dx:
+        _, wd = _gconv_images(weight, Cc, Cc // groups, False, True)
+        dxh = torch.empty(N, H, W, Cc, dtype=torch.bfloat16, device=x.device)      # (the launch writes every pixel)
+        d.x, d.ldx, d.w = dxh.data_ptr(), Cc, wd.data_ptr()
+        L.check(L.lib().mi_gconv_dgrad(C.byref(d), L.stream_ptr()), "mi_gconv_dgrad")
+        dx = _nchw(dxh, Cc)
+    if need_gw or need_gb:
+        xh = _nhwc_v(x)
+        gw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
+        if need_gb:
+            gb = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        need = L.check(L.lib().mi_gconv_wgrad_plan(C.byref(d), None), "mi_gconv_wgrad_plan")
+        ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=x.device)
+        d.x, d.ldx, d.gw, d.gbias, d.ws, d.ws_bytes = xh.data_ptr(), _ld(xh), gw.data_ptr(), (gb.data_ptr() if need_gb else None), ws.data_ptr(), ws.numel()
+        L.check(L.lib().mi_gconv_wgrad(C.byref(d), L.stream_ptr()), "mi_gconv_wgrad")
+        if not need_gw:
+            gw = none
+    return dx, gw, gb
+
+
+torch.library.impl(_LIBDEF, "conv2d_grouped", "CUDA")(_conv2d_grouped_cuda)
+torch.library.impl(_LIBDEF, "conv2d_grouped_backward", "CUDA")(_conv2d_grouped_backward_cuda)
+
+
+def _gconv_setup(ctx, inputs, output):
+    x, weight, bias, stride, padding, groups = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.has_bias, ctx.stride, ctx.padding, ctx.groups = bias is not None, stride, padding, groups
+
+
+def _gconv_bwd(ctx, grad):
+    x, weight = ctx.saved_tensors
+    need_dx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    need_gb = ctx.has_bias and ctx.needs_input_grad[2]
+    dx, gw, gb = torch.ops.mi355.conv2d_grouped_backward(grad, x, weight, need_dx, need_gw, need_gb, ctx.stride, ctx.padding, ctx.groups)
+    return (dx.to(x.dtype) if need_dx else None, gw.to(weight.dtype) if need_gw else None, gb if need_gb else None, None, None, None)
+
+
+torch.library.register_autograd("mi355::conv2d_grouped", _gconv_bwd, setup_context=_gconv_setup)
+
+
 # ------------------------------------------------------------------------------------------------ mi355::conv2d
 _LIBDEF.define("conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int padding) -> Tensor")
 _LIBDEF.define("conv2d_backward(Tensor grad, Tensor x, Tensor weight, bool has_bias, int stride, int padding, bool defer=False) -> (Tensor, Tensor, Tensor)")
@@ -1112,5 +1214,24 @@ def patch_base_convs(module):
     for m in module.modules():
         if _is_base_conv(m):
             m.forward = (lambda x, _m=m: base_conv_forward(_m, x))
+            n += 1
+    return n
+
+
+def _is_grouped_conv(m):
+    return (isinstance(m, torch.nn.Conv2d) and m.groups > 1 and tuple(m.kernel_size) == (3, 3) and tuple(m.padding) == (1, 1)
+            and tuple(m.dilation) == (1, 1) and tuple(m.stride) in ((1, 1), (2, 2)) and m.padding_mode == "zeros"
+            and m.in_channels == m.out_channels and m.in_channels % m.groups == 0 and m.in_channels // m.groups in GCONV_WIDTHS)
+
+
+def patch_grouped_convs(module):
+    """re-point the forward of every grouped 3x3 nn.Conv2d that torch.ops.mi355.conv2d_grouped serves (padding 1, dilation 1,
+    stride 1 or 2, square groups of 8 / 16 / 24 / 32 channels) to that op on the module's own weight and bias.  Depthwise,
+    dense and every other convolution are left alone.  Returns the number of patched modules.  state_dict, optimizers and
+    checkpoints are untouched: only `forward` changes."""
+    n = 0
+    for m in module.modules():
+        if _is_grouped_conv(m):
+            m.forward = (lambda x, _m=m: torch.ops.mi355.conv2d_grouped(x, _m.weight, _m.bias, _m.stride[0], 1, _m.groups))
             n += 1
     return n
