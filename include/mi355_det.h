@@ -399,6 +399,71 @@ int mi_bn_act_bwd_fused(const void* da, int ldda, const void* y, int ldy, const 
                         int64_t count, float* dgamma, float* dbeta, void* dy, int lddy, void* dres, int lddres,
                         int dres_accum, int64_t npix, int C, int act, uint32_t* barrier_words, mi_stream_t s);
 
+/* ---- train-mode BatchNorm + ReLU with a normed or plain residual (csrc/bn_relu.hip) ---------------
+ * The layers and the block tail of a RegNet / ResNet block whose norms use batch statistics (backbone/regnet.py builds
+ * detectron2's RegNet with norm = "SyncBN" and ReLU):  a = act(BN1(y1)),  a = act(BN1(y1) + BN2(y2))  (projection block
+ * tail) or  a = act(BN1(y1) + res)  (identity block tail), one launch each, ONE rounding at the store.
+ * Every tensor is a bf16 NHWC view (pointer, pixel stride) read and written in 16-byte pieces: C % 8 == 0, 0 < C <= 2048, every
+ * leading dimension a multiple of 8 and >= C, base pointers 16-byte aligned; anything else returns MI_EINVAL naming the
+ * quantity before any launch.  Channels [C, ld) of a row are never read and never written.
+ * Statistics are the fp64 slot accumulators [nslots][roundup(C, 32)][2] of the conv epilogue and of mi_bn_act_fwd (the caller
+ * zeroes them; nslots outside 1 .. MI_BN_SLOTS means MI_BN_SLOTS); block sums are fp32, added with fp64 atomics.
+ *
+ * mi_bn_stats: adds the per-channel (sum x, sum x^2) of a map into acc (slot = block % nslots) - for producers without a
+ * statistics epilogue (mi_gconv_fwd).  Channels >= C of a slot and slots >= nslots are untouched.
+ *
+ * mi_bn_relu_norm: one norm operand.  Forward, train mode (acc != NULL): the prologue sums the slots in slot order and derives
+ * scale / shift / mean / invstd; block 0 publishes them and updates running_mean / running_var / num_batches_tracked (each may
+ * be NULL) exactly as mi_bn_act_fwd does.  Eval mode (acc == NULL): scale / shift are inputs (mi_bn_eval_affine).  Backward:
+ * mean / invstd / gamma are inputs, dacc [nslots][roundup(C, 32)][2] receives (sum dz, sum dz * xhat) (zero on entry), dy / lddy
+ * the operand's gradient, dgamma / dbeta (may be NULL) fp32 [C], overwritten.
+ *
+ * mi_bn_relu_desc: n1 is mandatory; n2 (n2.y != NULL) and res are optional and exclude each other.
+ *   forward         a = bf16(act(y1 * scale1 + shift1 [+ y2 * scale2 + shift2 | + (float)res])), act = max(., 0) when relu, fp32
+ *   backward        dz = da where the saved output a > 0, else 0 (relu == 0: dz = da; a is then not read and may be NULL)
+ *     reduce        dacc_k += (sum dz, sum dz * xhat_k), xhat_k = (y_k - mean_k) * invstd_k, da and a read once for both operands
+ *     apply         finalises the sums in its prologue (fixed slot order) and writes
+ *                   dy_k = gamma_k * invstd_k * (dz - c1_k - xhat_k * c2_k), c = sums / count; dgamma_k = sum dz * xhat_k,
+ *                   dbeta_k = sum dz; dres (may be NULL) = dz, or += dz when `accumulate`.  dz is recomputed from (da, a) -
+ *                   except in the residual form with dres given and accumulate == 0: there REDUCE already writes dres = dz (it
+ *                   is the residual's gradient) and apply reads it back instead of (da, a), 7 tensor passes instead of 8; dres
+ *                   must then not alias da or a, and nothing may write it between the two launches. */
+typedef struct mi_bn_relu_norm {
+  const void* y;             /* raw convolution output; NULL in n2: operand absent                              */
+  const double* acc;         /* forward: statistics accumulators, NULL = eval mode                              */
+  const float* gamma;
+  const float* beta;
+  float* running_mean;
+  float* running_var;
+  int64_t* num_batches_tracked;
+  float* scale;
+  float* shift;
+  float* mean;
+  float* invstd;
+  double* dacc;              /* backward: (sum dz, sum dz * xhat) accumulators                                  */
+  void* dy;                  /* backward, apply: gradient of y                                                   */
+  float* dgamma;
+  float* dbeta;
+  int64_t count;             /* elements per channel behind the statistics (N * H * W)                          */
+  int32_t ldy, lddy, nslots, rsv_;
+  float eps, momentum;
+} mi_bn_relu_norm;
+typedef struct mi_bn_relu_desc {
+  mi_bn_relu_norm n1, n2;
+  const void* res;           /* forward: plain residual or NULL                                                 */
+  void* a;                   /* forward: output; backward: the saved output (read)                              */
+  const void* da;            /* backward: gradient of a                                                          */
+  void* dres;                /* backward, apply: gradient of res or NULL                                         */
+  int64_t npix;
+  int32_t ldres, lda, ldda, lddres;
+  int32_t C, relu, accumulate, rsv_;
+} mi_bn_relu_desc;
+int mi_bn_relu_desc_size(void);   /* sizeof(mi_bn_relu_desc) as compiled (binding self-check) */
+int mi_bn_stats(const void* x, int ldx, int64_t npix, int C, double* acc, int nslots, mi_stream_t s);
+int mi_bn_relu_fwd(const mi_bn_relu_desc* d, mi_stream_t s);
+int mi_bn_relu_bwd_reduce(const mi_bn_relu_desc* d, mi_stream_t s);
+int mi_bn_relu_bwd_apply(const mi_bn_relu_desc* d, mi_stream_t s);
+
 /* ---- data movement ops -------------------------------------------------- */
 /* Focus space-to-depth (wrappers.py:202-220) fused with fp32 NCHW -> bf16 NHWC and 12->16 ch pad */
 int mi_focus_pack(const float* img_nchw, int N, int H, int W, void* out, int ldo, mi_stream_t s);

@@ -116,6 +116,22 @@ class mi_gconv_desc(C.Structure):
                                          "dilation", "rsv_")]
 
 
+class mi_bn_relu_norm(C.Structure):
+    """one norm operand of mi_bn_relu_desc (csrc/bn_relu.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("y", "acc", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked",
+                                          "scale", "shift", "mean", "invstd", "dacc", "dy", "dgamma", "dbeta")] + \
+               [("count", C.c_int64)] + [(n, C.c_int32) for n in ("ldy", "lddy", "nslots", "rsv_")] + \
+               [("eps", C.c_float), ("momentum", C.c_float)]
+
+
+class mi_bn_relu_desc(C.Structure):
+    """train-mode BatchNorm + ReLU with a normed or a plain residual (csrc/bn_relu.hip): one record for the forward and both
+    backward passes"""
+    _fields_ = [("n1", mi_bn_relu_norm), ("n2", mi_bn_relu_norm)] + \
+               [(n, C.c_void_p) for n in ("res", "a", "da", "dres")] + [("npix", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("ldres", "lda", "ldda", "lddres", "C", "relu", "accumulate", "rsv_")]
+
+
 class mi_yolox_loss_desc(C.Structure):
     _fields_ = [
         ("preds", C.c_void_p), ("labels", C.c_void_p), ("anchors", C.c_void_p),
@@ -283,6 +299,11 @@ _PROTOS = {
     "mi_gconv_dgrad": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
     "mi_gconv_wgrad_plan": (C.c_int64, [C.POINTER(mi_gconv_desc), C.POINTER(C.c_int32)]),
     "mi_gconv_wgrad": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
+    "mi_bn_relu_desc_size": (C.c_int, []),
+    "mi_bn_stats": (C.c_int, [_vp, _i, _i64, _i, _vp, _i, _vp]),
+    "mi_bn_relu_fwd": (C.c_int, [C.POINTER(mi_bn_relu_desc), _vp]),
+    "mi_bn_relu_bwd_reduce": (C.c_int, [C.POINTER(mi_bn_relu_desc), _vp]),
+    "mi_bn_relu_bwd_apply": (C.c_int, [C.POINTER(mi_bn_relu_desc), _vp]),
     "mi_upsample2x_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "mi_upsample2x_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mi_spp_pool_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

@@ -155,6 +155,8 @@ def add_yolo_config(cfg):
         "ENC_LAYERS": 6, "DEC_LAYERS": 6, "PRE_NORM": False, "BBOX_EMBED_NUM_LAYERS": 3, "HIDDEN_DIM": 256,
         "NUM_OBJECT_QUERIES": 100, "NUM_QUERY_POSITION": 300, "NUM_QUERY_PATTERN": 3, "SPATIAL_PRIOR": "learned",
     })
+    # yolov7/config.py:41-43 (build_regnet_backbone)
+    _C.MODEL.REGNETS = CN({"TYPE": "x", "OUT_FEATURES": ["s2", "s3", "s4"]})
     _C.MODEL.BACKBONE.SIMPLE = False
     _C.MODEL.BACKBONE.STRIDE = 1
     _C.MODEL.BACKBONE.CHANNEL = 0

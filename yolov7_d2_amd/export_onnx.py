@@ -320,6 +320,10 @@ class _NetEmitter:
             # timm's resnet50d / resnet101d (modeling/resnet_vd.py): deep stem and pooled shortcuts are not written here
             raise NotImplementedError("export_onnx: no emitter for the ResNet-vd backbone (build_resnet_vd_backbone, ResNetVD): "
                                       "only detectron2's ResNet (build_resnet_backbone) is exported")
+        if type(bb).__name__ in ("RegNet", "AnyNet"):
+            # detectron2's RegNet (modeling/regnet.py): train-mode norms and grouped 3x3 blocks are not written here
+            raise NotImplementedError("export_onnx: no emitter for the RegNet backbone (build_regnet_backbone, RegNet): "
+                                      "only detectron2's ResNet (build_resnet_backbone) is exported")
         if any(type(m).__name__ == "DeformConv" for m in bb.modules()):
             # ONNX has no deformable convolution of this definition (opset 19's DeformConv is the modulated torchvision form)
             raise NotImplementedError("export_onnx: the backbone holds a DeformConv (MODEL.RESNETS.DEFORM_ON_PER_STAGE): "

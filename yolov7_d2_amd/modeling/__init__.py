@@ -13,6 +13,7 @@ from .position_encoding import PositionEmbeddingSine
 from .detr import DETR, MLP
 from .resnet import ResNet, build_resnet_backbone, FrozenBatchNorm2d, DeformConv, DeformBottleneckBlock
 from .resnet_vd import ResNetVD, BottleneckVD, build_resnet_vd_backbone
+from .regnet import RegNet, AnyNet, AnyStage, ResBottleneckBlock, BottleneckTransform, SimpleStem, build_regnet_backbone
 from .box_ops import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh, box_iou, generalized_box_iou
 from .detr_meta import (Detr, Joiner, MaskedBackbone, MaskedBackboneTraceFriendly, NestedTensor, PostProcess,
                         nested_tensor_from_tensor_list)

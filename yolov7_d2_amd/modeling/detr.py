@@ -11,6 +11,7 @@ ResNet-50, an un-vendored dependency: SURVEY a36, not rebuilt here).
 """
 import torch
 from torch import nn
+import torch.nn.functional as F
 
 from .. import _lib as L
 from .transformer import _LinearFn, _tok
@@ -82,6 +83,8 @@ class DETR(nn.Module):
         #  first and the NHWC one from it were two 18 MB passes per step)
         tok = _tok(src.permute(0, 2, 3, 1)).reshape(B * H * W, Cc)
         w = self.input_proj.weight.view(self.input_proj.out_channels, Cc)
+        if Cc % 32:     # the row GEMM takes k-chunks of 32: zero columns on both sides (RegNetX_200MF hands over 368 channels)
+            tok, w = F.pad(tok, (0, -Cc % 32)), F.pad(w, (0, -Cc % 32))
         proj = _LinearFn.apply(tok, w, self.input_proj.bias)
         proj = proj.reshape(B, H, W, -1).permute(0, 3, 1, 2)
         hs = self.transformer(proj, mask, self.query_embed.weight, pos[-1])[0]
