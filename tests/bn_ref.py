@@ -32,7 +32,7 @@ every case - assert_fwd_conditions / assert_bwd_conditions - before anything is 
     rcp(1 + __expf(-z))) is then exactly 1 (1 + e == 1 in fp32 for e < 2^-24, rcp(1) = 1) or exactly 0 (__expf overflows to
     +inf for -z > 88.8, rcp(inf) = 0): the forward gives z or -0, act' = s * (1 + z * (1 - s)) is 1 or 0.  The reference uses
     these limits (sat_sigmoid) - the premise is checked on the device first (test_premise_*) - so the ACT = 1 instantiations,
-    MODE 1 (dz kept in registers) included, are bit-exact too.
+    the one-launch backward (dz kept in registers) included, are bit-exact too.
 """
 import collections
 import math
@@ -226,17 +226,15 @@ def tpb(C):
     return C8, 256 // C8, (256 // C8) * C8
 
 
-def ew_blocks(total, per=512):
-    """grid of the streaming kernels (ew_blocks of csrc/bn_act.hip; per = MI_BN_EW_ITEMS, honoured from 256)"""
-    ipb = per if per >= 256 else 512
-    return max(1, min(1024, -(-total // ipb)))
+def ew_blocks(total):
+    """grid of the streaming kernels (ew_blocks of csrc/bn_act.hip: BN_EW_ITEMS = 512 items per block, at most 1024 blocks)"""
+    return max(1, min(1024, -(-total // 512)))
 
 
-def fused_blocks(npix, C, cap, ipt=4):
-    """grid of the one-launch backward (bn_fused_blocks; ipt = MI_BN_FUSED_ITEMS, honoured in 1 .. 16)"""
+def fused_blocks(npix, C, cap):
+    """grid of the one-launch backward (bn_fused_blocks: BN_FUSED_ITEMS = 4 items per thread, at most cap blocks)"""
     C8, _, T = tpb(C)
-    ipt = ipt if 1 <= ipt <= 16 else 4
-    return max(1, min(cap, -(-npix * C8 // (T * ipt))))
+    return max(1, min(cap, -(-npix * C8 // (T * 4))))
 
 
 def nmine_set(npix, C, nb):
@@ -447,10 +445,19 @@ def bwd_cases():
     ]
 
 
+def bwd_cap_cases():
+    """just beyond the 1024-block cap of the streaming kernels: 2100 x 256 = 537 600 items > 1024 x 256 x 2, a thread of the
+    2-deep apply loop takes a third item (a second trip); identity with accumulated dres, and its saturated-SiLU twin with
+    dres overwritten"""
+    lds = (2056, 2064, 2048, 2072)
+    return [BwdCase("b-c2048-n2100-cap", 2048, 2100, 16, 8, 0, 2, lds, 1024, 0, False, 15),
+            BwdCase("b-c2048-n2100-cap-sat", 2048, 2100, 16, 8, "sat", 1, lds, 1024, 0, False, 16)]
+
+
 def fused_capacity_cases():
     """mi_bn_fused_set_capacity(cap) pins the grid of the one-launch backward at nb = cap in {1, 2, 15, 16, 17, 33} (one block;
     fewer blocks than barrier groups; the two-level barrier with even and uneven groups) and npix = nb * PL * m + r gives its
-    threads m or m + 1 items, either side of the register capacities R = 14 (MODE 1) and 16 (MODE 0), with odd tails for the
+    threads m or m + 1 items, either side of the on-chip capacity R = 14 (and of 16), with odd tails for the
     4-deep and 2-deep streaming loops: {13, 14}, {15, 16}, {16, 17}, {19, 20}, {13, 14}, {17, 18}, {14, 15}; b-c8-n5-cap1 has
     threads without any item"""
     B = BwdCase
@@ -550,29 +557,15 @@ def group_cases():
 
 # ------------------------------------------------------------------------------------------------ instantiations (coverage)
 def instantiations():
-    """every kernel instantiation of csrc/bn_act.hip, and the legacy phase-2 path of the one-launch backward, by the process
-    that can reach it (MI_BN_FUSED_MODE and MI_BN_BWD_LAST are read once per process): "default", "mode0", "legacy" """
-    t = {}
-    for a in (0, 1):
-        for k in ("bn_act_fwd", "bn_bwd_reduce", "bn_bwd_apply"):
-            t["%s_kernel<%d>" % (k, a)] = "default"
-            t["%s_group_kernel<%d>" % (k, a)] = "default"
-        for m in (0, 1):
-            t["bn_bwd_fused_kernel<%d, %d>" % (a, m)] = "default" if m else "mode0"
-            t["bn_bwd_fused_group_kernel<%d, %d>" % (a, m)] = "default" if m else "mode0"
-    t["legacy phase 2"] = "legacy"
-    t["legacy phase 2 (group)"] = "legacy"
-    return t
+    """every kernel instantiation of csrc/bn_act.hip: the three streaming kernels and the one-launch backward, each with the
+    activation off / on, single and grouped - 16"""
+    return ["%s%s_kernel<%d>" % (k, g, a) for k in ("bn_act_fwd", "bn_bwd_reduce", "bn_bwd_apply", "bn_bwd_fused")
+            for g in ("", "_group") for a in (0, 1)]
 
 
-def kernel_name(stem, act, env, group=False):
-    """the instantiation a launch runs, by the dispatch of the entry points (act != 0 -> <1>; MODE = MI_BN_FUSED_MODE != 0)"""
-    a = 1 if act else 0
-    g = "_group" if group else ""
-    if stem == "bn_bwd_fused":
-        mode = 0 if env.get("MI_BN_FUSED_MODE", "1").strip() in ("0",) else 1
-        return "bn_bwd_fused%s_kernel<%d, %d>" % (g, a, mode)
-    return "%s%s_kernel<%d>" % (stem, g, a)
+def kernel_name(stem, act, group=False):
+    """the instantiation a launch runs, by the dispatch of the entry points (act != 0 -> <1>)"""
+    return "%s%s_kernel<%d>" % (stem, "_group" if group else "", 1 if act else 0)
 
 
 # ------------------------------------------------------------------------------------------------------- derived bounds
@@ -653,7 +646,7 @@ def fwd_mutation_case():
 
 
 def bwd_mutation_case():
-    """2 blocks x 21 lanes, 17 or 18 items per thread: item R exists for R = 14 and R = 16"""
+    """2 blocks x 21 lanes, 17 or 18 items per thread: item R exists for R = 14 (and for 16)"""
     return BwdCase("mut-bwd", 96, 2 * 21 * 17 + 20, 3, 8, 0, 2, (104, 96, 112, 128), 3, 2, False, 32)
 
 

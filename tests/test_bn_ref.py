@@ -133,7 +133,14 @@ def test_forward_cap_case_makes_a_second_partial_trip():
     assert R.ew_blocks(total) == 1024 and 1024 * T * 4 < total < 1024 * T * 5
 
 
-@pytest.mark.parametrize("c", R.bwd_cases() + R.fused_capacity_cases() + [R.bwd_mutation_case()], ids=lambda c: c.name)
+def test_backward_cap_cases_give_the_apply_loop_a_third_item():
+    for c in R.bwd_cap_cases():
+        C8, _, T = R.tpb(c.C)
+        total = c.npix * C8
+        assert c.nblk == R.ew_blocks(total) == 1024 and 1024 * T * 2 < total < 1024 * T * 3
+
+
+@pytest.mark.parametrize("c", R.bwd_cases() + R.bwd_cap_cases() + R.fused_capacity_cases() + [R.bwd_mutation_case()], ids=lambda c: c.name)
 def test_backward_family_conditions_and_fp32_emulation(c):
     """the conditions hold on every backward case, and an fp32 evaluation with the channel sums taken in two different
     orders (torch's pairwise sum; a sequential sum over the reversed pixels, in blocks of 7) gives dy, dgamma, dbeta, dres
@@ -208,9 +215,9 @@ def test_leading_dimensions_differ_pairwise_in_one_case_per_entry_point():
 
 def test_instantiation_table_is_complete():
     t = R.instantiations()
-    assert len(t) == 2 * 3 * 2 + 2 * 2 * 2 + 2 and set(t.values()) == {"default", "mode0", "legacy"}
-    assert R.kernel_name("bn_bwd_fused", "sat", {"MI_BN_FUSED_MODE": "0"}, True) == "bn_bwd_fused_group_kernel<1, 0>"
-    assert R.kernel_name("bn_bwd_fused", 0, {}) == "bn_bwd_fused_kernel<0, 1>" and R.kernel_name("bn_act_fwd", 1, {}) in t
+    assert len(t) == len(set(t)) == 2 * 4 * 2                   # 6 streaming + 2 one-launch, single and grouped
+    assert R.kernel_name("bn_bwd_fused", "sat", True) == "bn_bwd_fused_group_kernel<1>"
+    assert R.kernel_name("bn_bwd_fused", 0) == "bn_bwd_fused_kernel<0>" and R.kernel_name("bn_act_fwd", 1) in t
 
 
 def test_sigmoid_bounds_hold_for_an_fp32_emulation_and_are_not_vacuous():

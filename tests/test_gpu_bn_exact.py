@@ -1,5 +1,5 @@
 """GPU (-m gpu): the BatchNorm(train) + SiLU (+ residual) family csrc/bn_act.hip - the three streaming kernels, the one-launch
-backward that keeps registers and LDS across a grid-wide barrier (both retention modes, the legacy post-barrier path), the
+backward that keeps registers and LDS across a grid-wide barrier, the
 grouped forms of all four and mi_bn_eval_affine - against the plain float64 reference of tests/bn_ref.py with NO tolerance,
 through the C ABI by ctypes, on every pass and launch form.
 
@@ -19,17 +19,11 @@ are pairwise different in at least one case per entry point.
 
 What the exact families cannot reach - the sigmoid itself, real statistics - is held to derived bounds: an exhaustive sweep
 of SiLU and SiLU' over every finite bf16 argument, and Gaussian data with elementwise bounds (bn_ref.numerics_*), each bound
-first checked against an fp32 emulation on the host.  The process-wide switches (MI_BN_FUSED_MODE, MI_BN_BWD_LAST,
-MI_BN_EW_ITEMS, MI_BN_FUSED_ITEMS: function-local statics read once) run the exact families again in fresh children.  The
-launched instantiations are counted and the table must be complete."""
+first checked against an fp32 emulation on the host.  The launched instantiations are counted and the table must be
+complete."""
 import collections
 import ctypes as C
-import json
 import math
-import os
-import subprocess
-import sys
-import time
 import types
 
 import pytest
@@ -45,25 +39,11 @@ GUARD = 64                     # guard elements around every buffer (>= 64 bytes
 NAN = float("nan")
 F64 = torch.float64
 BF, F32 = torch.bfloat16, torch.float32
-CHILD_TIMEOUT = 120            # seconds, as for the attention child (tests/test_gpu_mha_exact.py); each child measured 3.0 - 3.3 s on an MI355X, most of it starting torch
 SEEN = collections.Counter()   # instantiation -> launches by an exact family in this process
-ENV_KEYS = ("MI_BN_FUSED_MODE", "MI_BN_BWD_LAST", "MI_BN_EW_ITEMS", "MI_BN_FUSED_ITEMS")
 
 
 def sp():
     return L.stream_ptr()
-
-
-def env_int(name, default):
-    return int(os.environ[name]) if os.environ.get(name) else default
-
-
-def default_switches_here():
-    assert not any(os.environ.get(k) for k in ENV_KEYS), "this process must run with the launcher's switches unset (they are read once)"
-
-
-def legacy_here():
-    return os.environ.get("MI_BN_BWD_LAST") is not None and env_int("MI_BN_BWD_LAST", 1) == 0
 
 
 class Buf:
@@ -175,7 +155,7 @@ class FwdJob:
     def launch(self):
         L.check(L.lib().mi_bn_act_fwd(*self.args()), "mi_bn_act_fwd")
         torch.cuda.synchronize()
-        SEEN[R.kernel_name("bn_act_fwd", self.c.act, os.environ)] += 1
+        SEEN[R.kernel_name("bn_act_fwd", self.c.act)] += 1
 
     def check(self, r, i=0):
         """complaints after launch number i (0-based) against the reference r of fwd_reference"""
@@ -265,14 +245,14 @@ class BwdJob:
         c, lib = self.c, L.lib()
         L.check(lib.mi_bn_act_bwd_reduce(*self.head(), self.dacc.ptr, c.nslots, c.nblk, c.npix, c.C, 1 if c.act else 0, sp()), "reduce")
         torch.cuda.synchronize()
-        SEEN[R.kernel_name("bn_bwd_reduce", c.act, os.environ)] += 1
+        SEEN[R.kernel_name("bn_bwd_reduce", c.act)] += 1
         mid = self.check_sums("reduce", folded=False)
         for b in (self.dy, self.dres if c.dres == 1 else None, self.dgamma, self.dbeta):      # reduce writes nothing else
             if b is not None and not bool(b.view().isnan().all()):
                 mid.append("%s: written by the reduce launch" % c.name)
         L.check(lib.mi_bn_act_bwd_apply(*self.head(), self.gamma.ptr, self.dacc.ptr, c.nslots, self.o.count, *self.tail(), sp()), "apply")
         torch.cuda.synchronize()
-        SEEN[R.kernel_name("bn_bwd_apply", c.act, os.environ)] += 1
+        SEEN[R.kernel_name("bn_bwd_apply", c.act)] += 1
         return mid
 
     def fused(self):
@@ -280,9 +260,7 @@ class BwdJob:
         L.check(L.lib().mi_bn_act_bwd_fused(*self.head(), self.gamma.ptr, self.dacc.ptr, c.nslots, self.o.count, *self.tail(),
                                             self.bar.ptr, sp()), "fused")
         torch.cuda.synchronize()
-        SEEN[R.kernel_name("bn_bwd_fused", c.act, os.environ)] += 1
-        if legacy_here():
-            SEEN["legacy phase 2"] += 1
+        SEEN[R.kernel_name("bn_bwd_fused", c.act)] += 1
 
     def check_sums(self, what, folded):
         """the accumulators: NaN pattern and guards intact, and the live slots hold the channel sums - exactly (every partial
@@ -348,7 +326,7 @@ def run_fused_case(c, stats=None):
     bad = []
     try:
         cap = effective_capacity(c.cap)
-        nb = R.fused_blocks(c.npix, c.C, cap, env_int("MI_BN_FUSED_ITEMS", 4))
+        nb = R.fused_blocks(c.npix, c.C, cap)
         assert nb <= cap
         if stats is not None:
             stats["nb"].add(nb)
@@ -357,7 +335,7 @@ def run_fused_case(c, stats=None):
             job.refill()
             job.fused()
             bad += job.check("fused, launch %d, %d blocks" % (i + 1, nb))
-            bad += job.check_sums("fused", folded=not legacy_here())
+            bad += job.check_sums("fused", folded=True)
             bad += job.check_barrier([nb] * (i + 1))
     finally:
         L.lib().mi_bn_fused_set_capacity(0)
@@ -386,7 +364,7 @@ def plan_group(kind, jobs, act):
 def run_group(meta, tab, stem, act):
     L.check(L.lib().mi_bn_group_run(C.byref(meta), tab.ptr, sp()), "mi_bn_group_run")
     torch.cuda.synchronize()
-    SEEN[R.kernel_name(stem, act, os.environ, group=True)] += 1
+    SEEN[R.kernel_name(stem, act, group=True)] += 1
     assert tab.complaint("table", tab.view()) is None
 
 
@@ -401,8 +379,7 @@ def run_group_case(g):
             jobs.append(FwdJob(c, o))
             refs.append(R.fwd_reference(c, o, 1))
         meta, tab, starts = plan_group(0, jobs, g.act)
-        assert [b - a for a, b in zip(starts, starts[1:])] == [
-            R.ew_blocks(c.npix * c.C // 8, env_int("MI_BN_EW_ITEMS", 512)) for c in g.jobs]
+        assert [b - a for a, b in zip(starts, starts[1:])] == [R.ew_blocks(c.npix * c.C // 8) for c in g.jobs]
         run_group(meta, tab, "bn_act_fwd", g.act)
         for job, r in zip(jobs, refs):
             bad += job.check(r, 0)
@@ -424,10 +401,9 @@ def run_group_case(g):
     # kind 3: a small capacity, so that the jobs SHARE it (want > cap): a third of what they would take, at least n + 1
     try:
         hw = effective_capacity(0)
-        ipt = env_int("MI_BN_FUSED_ITEMS", 4)
-        want = sum(R.fused_blocks(c.npix, c.C, hw, ipt) for c in g.jobs)
+        want = sum(R.fused_blocks(c.npix, c.C, hw) for c in g.jobs)
         cap = effective_capacity(max(g.n + 1, want // 3))
-        want = sum(R.fused_blocks(c.npix, c.C, cap, ipt) for c in g.jobs)
+        want = sum(R.fused_blocks(c.npix, c.C, cap) for c in g.jobs)
         assert want > cap or g.n == 1, (want, cap)
         meta, tab, starts = plan_group(3, jobs, g.act)
         nbs = [b - a for a, b in zip(starts, starts[1:])]
@@ -436,11 +412,9 @@ def run_group_case(g):
             for job in jobs:
                 job.refill()
             run_group(meta, tab, "bn_bwd_fused", g.act)
-            if legacy_here():
-                SEEN["legacy phase 2 (group)"] += 1
             for job, nb in zip(jobs, nbs):
                 bad += job.check("grouped fused, launch %d, %d blocks" % (i + 1, nb))
-                bad += job.check_sums("grouped fused", folded=not legacy_here())
+                bad += job.check_sums("grouped fused", folded=True)
                 bad += job.check_barrier([nb] * (i + 1))
     finally:
         L.lib().mi_bn_fused_set_capacity(0)
@@ -504,6 +478,31 @@ def test_forward_exact_beyond_the_block_cap():
     assert bad == [], bad[:10]
 
 
+def one_job_group(kind, c):
+    return types.SimpleNamespace(kind=kind, n=1, act=c.act, jobs=[c])
+
+
+def test_forward_exact_beyond_the_block_cap_grouped():
+    """the same case as a one-job group of kind 0: the grouped body makes the second trip too"""
+    bad = run_group_case(one_job_group(0, R.fwd_cap_case()))
+    assert bad == [], bad[:10]
+
+
+@pytest.mark.parametrize("c", R.bwd_cap_cases(), ids=lambda c: c.name)
+def test_backward_two_pass_exact_beyond_the_block_cap(c):
+    """2100 x 2048: 537 600 items on the 1024-block cap - a thread of the 2-deep apply loop takes a third item (a second,
+    partial trip); the 1024 reduce blocks (one pixel lane each) take 2 or 3 pixels"""
+    bad = run_two_pass_case(c)
+    assert bad == [], bad[:10]
+
+
+@pytest.mark.parametrize("c", R.bwd_cap_cases(), ids=lambda c: c.name)
+def test_backward_two_pass_exact_beyond_the_block_cap_grouped(c):
+    """the same cases as a one-job group of kind 12 (reduce, then apply on its sums)"""
+    bad = run_group_case(one_job_group(12, c))
+    assert bad == [], bad[:10]
+
+
 @pytest.mark.parametrize("c", R.bwd_cases(), ids=lambda c: c.name)
 def test_backward_two_pass_exact(c):
     """mi_bn_act_bwd_reduce + mi_bn_act_bwd_apply: the forward's shapes, nblk 1 / 3 / more blocks than pixel lanes of work /
@@ -526,7 +525,6 @@ def test_backward_fused_exact(c):
 def test_fused_capacity_cases_reach_the_grids_and_item_counts():
     """what mi_bn_fused_set_capacity returns for the capacity cases is what they ask for (the device holds more), so the
     launcher's grid is the pinned one: nb in {1, 2, 15, 16, 17, 33}, items per thread 0, 1, 13 .. 20"""
-    default_switches_here()
     stats = dict(nb=set(), items=set())
     try:
         for c in R.fused_capacity_cases():
@@ -805,7 +803,7 @@ def test_random_data_within_derived_bounds(nc):
             L.check(L.lib().mi_bn_act_bwd_reduce(*bj.head(), bj.dacc.ptr, bc.nslots, nb, bc.npix, bc.C, 1, sp()), "reduce")
             L.check(L.lib().mi_bn_act_bwd_apply(*bj.head(), bj.gamma.ptr, bj.dacc.ptr, bc.nslots, o.count, *bj.tail(), sp()), "apply")
         else:
-            nb = R.fused_blocks(bc.npix, bc.C, L.lib().mi_bn_fused_set_capacity(0), env_int("MI_BN_FUSED_ITEMS", 4))
+            nb = R.fused_blocks(bc.npix, bc.C, L.lib().mi_bn_fused_set_capacity(0))
             L.check(L.lib().mi_bn_act_bwd_fused(*bj.head(), bj.gamma.ptr, bj.dacc.ptr, bc.nslots, o.count, *bj.tail(), bj.bar.ptr, sp()), "fused")
         torch.cuda.synchronize()
         for name, b in (("dy", bj.dy), ("dres", bj.dres), ("dgamma", bj.dgamma), ("dbeta", bj.dbeta)):
@@ -863,7 +861,7 @@ def mutants_on_device():
     job = make_bwd_job(c)
     try:
         cap = effective_capacity(c.cap)
-        nb = R.fused_blocks(c.npix, c.C, cap, env_int("MI_BN_FUSED_ITEMS", 4))
+        nb = R.fused_blocks(c.npix, c.C, cap)
         job.refill()
         job.fused()
     finally:
@@ -871,70 +869,19 @@ def mutants_on_device():
     assert job.check("fused") == []
     got = dict(dy=job.dy.view(), dgamma=job.dgamma.view().reshape(-1), dbeta=job.dbeta.view().reshape(-1), dres=job.dres.view())
     ref = R.bwd_outputs(job.r)
-    mode1 = R.kernel_name("bn_bwd_fused", c.act, os.environ).endswith("1>")
-    muts = R.bwd_mutants(c, job.o, job.r, nb, 14 if mode1 else 16, job.da.from_view())
+    muts = R.bwd_mutants(c, job.o, job.r, nb, 14, job.da.from_view())
     assert len(muts) == 4
     for name, (exact, old) in muts.items():
         assert not all(R.same(got[k], exact[k]) for k in ref), name
         assert R.old_criteria_accept(ref, old), name
 
 
-# ----------------------------------------------------------------------------------- the switches, in children; coverage
-def run_exact_sweep():
-    """what a child runs: the exact families on the entry points its switch reaches, and the mutants; -> complaints"""
-    bad = []
-    streaming = bool(os.environ.get("MI_BN_EW_ITEMS"))       # the switch of the streaming kernels; the others: the one-launch form
-    if streaming:
-        for c in R.fwd_cases():
-            bad += run_fwd_case(c, launches=2)
-        for c in R.bwd_cases():
-            bad += run_two_pass_case(c)
-    else:
-        for c in R.bwd_cases() + R.fused_capacity_cases():
-            bad += run_fused_case(c)
-    for g in R.group_cases():
-        if (g.kind != 3) == streaming:
-            bad += run_group_case(g)
-    try:
-        mutants_on_device()
-    except AssertionError as e:
-        bad.append(("mutants: %s" % e)[:400])
-    return bad
 
 
-CHILDREN = {"mode0": {"MI_BN_FUSED_MODE": "0"}, "legacy": {"MI_BN_BWD_LAST": "0"}, "ew4096": {"MI_BN_EW_ITEMS": "4096"},
-            "items16": {"MI_BN_FUSED_ITEMS": "16"}}
-
-
-@pytest.mark.parametrize("which", list(CHILDREN), ids=list(CHILDREN))
-def test_switches_in_a_child(which):
-    """MI_BN_FUSED_MODE, MI_BN_BWD_LAST, MI_BN_EW_ITEMS and MI_BN_FUSED_ITEMS are function-local statics of csrc/bn_act.hip read
-    once per process: the exact families run again in a fresh child per setting - MODE 0 (da and y kept in registers as
-    loaded), the legacy phase 2 (every block reads every slot), 4096 items per block of the streaming kernels (several trips of
-    their loops at these shapes), 16 items per thread of the one-launch form.  The child prints one JSON line; it must have
-    launched the instantiations only its setting reaches.  A child that ends abnormally fails the test at once; nothing
-    more is started."""
-    env = dict(os.environ, **CHILDREN[which])
-    t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "bn_exact_gpu_child.py")],
-                       env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    print("child wall time %.1f s" % (time.time() - t0))
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    out = json.loads(r.stdout.strip().splitlines()[-1])
-    assert out["env"] == CHILDREN[which]
-    assert out["bad"] == [], out["bad"][:20]
-    need = [k for k, v in R.instantiations().items() if v == which]
-    if which in ("ew4096", "items16"):
-        need = [k for k, v in R.instantiations().items() if v == "default" and ("fused" in k) == (which == "items16")]
-    assert need and all(out["seen"].get(k, 0) > 0 for k in need), (need, out["seen"])
-
-
+# ------------------------------------------------------------------------------------------------------------- coverage
 def test_every_instantiation_is_launched_by_an_exact_family():
-    """the counted table: in this process (default switches) the exact families launch every instantiation that the default
-    dispatch reaches - the six streaming kernels, the two MODE 1 forms of the one-launch backward, and the grouped forms of
-    all eight; the MODE 0 forms and the legacy phase 2 are required of their children (test_switches_in_a_child); together
-    that is every entry of bn_ref.instantiations()"""
-    default_switches_here()
+    """the counted table: in this process the exact families launch every entry of bn_ref.instantiations() - the six
+    streaming kernels, the two forms of the one-launch backward, and the grouped forms of all eight: 16"""
     SEEN.clear()
     bad = []
     for c in R.fwd_cases()[:4]:
@@ -946,8 +893,7 @@ def test_every_instantiation_is_launched_by_an_exact_family():
     assert bad == [], bad[:10]
     table = R.instantiations()
     for k in sorted(table):
-        print("%-40s %-8s %d" % (k, table[k], SEEN.get(k, 0)))
-    assert set(SEEN) <= set(table), set(SEEN) - set(table)
-    missing = [k for k, v in table.items() if v == "default" and SEEN.get(k, 0) == 0]
+        print("%-40s %d" % (k, SEEN.get(k, 0)))
+    assert len(table) == 16 and set(SEEN) <= set(table), set(SEEN) - set(table)
+    missing = [k for k in table if SEEN.get(k, 0) == 0]
     assert missing == [], missing
-    assert set(table.values()) == {"default", "mode0", "legacy"} <= {"default"} | set(CHILDREN)

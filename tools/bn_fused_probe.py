@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """BatchNorm backward, two-pass (reduce + apply) vs the one-launch fused kernel, per layer shape of YOLOX-s at 16x640x640.
-Rotates over NSET buffer sets so that every launch reads from HBM.  MI_BN_FUSED_MODE selects the retention variant."""
+Rotates over NSET buffer sets so that every launch reads from HBM."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,7 +13,7 @@ shapes = [(32, 16 * 320 * 320), (64, 16 * 160 * 160), (32, 16 * 160 * 160), (128
           (256, 16 * 40 * 40), (128, 16 * 40 * 40), (512, 16 * 20 * 20), (256, 16 * 20 * 20)]
 NSET = int(os.environ.get("NSET", 4)); IT = int(os.environ.get("IT", 24))
 sp = L.stream_ptr()
-print("capacity", lib.mi_bn_fused_set_capacity(int(os.environ.get("CAP", 0))), "mode", os.environ.get("MI_BN_FUSED_MODE", "1"))
+print("capacity", lib.mi_bn_fused_set_capacity(int(os.environ.get("CAP", 0))))
 for C, npix in shapes:
     ld = (C + 31) // 32 * 32
     sets = []

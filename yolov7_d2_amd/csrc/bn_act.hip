@@ -17,16 +17,27 @@
 //   * bn_bwd_reduce accumulates (sum dz, sum dz*xhat) the same way and bn_bwd_apply finalizes in its prologue.
 // fp64 accumulation of fp32 tile sums makes the result independent of the atomic arrival order except in
 // astronomically rare rounding ties.  All kernels are HBM streams: 16-byte (8 x bf16) accesses, fp32 math.
+// The statistics arithmetic, the prologues and the block reduction are bn_common.h's (shared with bn_relu.hip and the conv
+// kernels); the grid barrier is conv_bn.h's.
+#include <stdio.h>
 #include <string.h>
-#include <stdlib.h>
 #include "common.h"
+#include "bn_common.h"
 #include "conv_bn.h"
 
-#define BN_MAXC 2048
-// accumulator layout: [slot][CA][2] with CA = C rounded up to 32 - the CoutPad the conv epilogue adds its tile sums with
-#define BN_ACC_C(C) (((C) + 31) / 32 * 32)
-// every tensor access is a 16-byte vector: NULL (an absent optional tensor) passes
-static inline bool bn_al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+// the activation picks the instantiation: written once for the single-layer and the grouped kernel of each pass
+#define BN_LAUNCH(kern, act, nblocks, st, ...)                                                          \
+  do {                                                                                                  \
+    if (act) hipLaunchKernelGGL(kern<1>, dim3(nblocks), dim3(256), 0, (hipStream_t)(st), __VA_ARGS__);  \
+    else hipLaunchKernelGGL(kern<0>, dim3(nblocks), dim3(256), 0, (hipStream_t)(st), __VA_ARGS__);      \
+  } while (0)
+// a single-layer entry point states its arguments as the job record of the grouped form: one filler checks and fills both
+static mi_bn_job bn_job(int64_t npix, int C, int nslots, int act) {
+  mi_bn_job b;
+  memset(&b, 0, sizeof(b));
+  b.npix = npix; b.C = C; b.nslots = nslots; b.act = act;
+  return b;
+}
 
 // ------------------------------------------------------------------ eval-mode affine
 __global__ void bn_eval_affine_kernel(const float* gamma, const float* beta, const float* rm, const float* rv,
@@ -72,47 +83,7 @@ struct BnFwdK {
 template <int ACT, class PK>
 __device__ __forceinline__ void bn_act_fwd_body(PK& p, const int bid, const int nb) {
   __shared__ float s_sc[BN_MAXC], s_sh[BN_MAXC];
-  const int C = p.C8 * 8, CA = BN_ACC_C(C);
-  if (p.acc) {
-    for (int c = threadIdx.x; c < C; c += 256) {
-      // all slot loads are issued before the first add (a rolled loop serialises 16 L2 round trips: ~4.5 us)
-      f64x2 v[MI_BN_SLOTS];
-#pragma unroll
-      for (int k = 0; k < MI_BN_SLOTS; ++k)
-        v[k] = k < p.nslots ? *(const f64x2*)(p.acc + ((size_t)k * CA + c) * 2) : f64x2{0.0, 0.0};
-      double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-      for (int k = 0; k < MI_BN_SLOTS; ++k) {
-        s1 += v[k][0];
-        s2 += v[k][1];
-      }
-      const double mean = s1 * p.inv_count;
-      double var = s2 * p.inv_count - mean * mean;
-      if (var < 0.0) var = 0.0;
-      const double invstd = 1.0 / sqrt(var + (double)p.eps);
-      const float g = p.gamma[c], b = p.beta[c];
-      const float sc = (float)((double)g * invstd);
-      const float sh = (float)((double)b - mean * (double)g * invstd);
-      s_sc[c] = sc;
-      s_sh[c] = sh;
-      if (bid == 0) {
-        p.scale[c] = sc;
-        p.shift[c] = sh;
-        p.mean[c] = (float)mean;
-        p.invstd[c] = (float)invstd;
-        if (p.rmean) {
-          p.rmean[c] = (1.f - p.momentum) * p.rmean[c] + p.momentum * (float)mean;
-          p.rvar[c] = (1.f - p.momentum) * p.rvar[c] + p.momentum * (float)(var * p.unbias);
-        }
-        if (c == 0 && p.nbt) *p.nbt += 1;
-      }
-    }
-  } else {
-    for (int c = threadIdx.x; c < C; c += 256) {
-      s_sc[c] = p.scale[c];
-      s_sh[c] = p.shift[c];
-    }
-  }
+  bn_fwd_prologue<true>(p, p.C8 * 8, bid, s_sc, s_sh);
   __syncthreads();
   const int C8 = p.C8;
   const int64_t total = p.npix * C8;
@@ -187,13 +158,35 @@ __global__ __launch_bounds__(256) void bn_act_fwd_group_kernel(const BnFwdK* __r
 // 4 blocks per CU; 512 items (two 16-byte items per thread) per block: the 20x20 / 40x40 maps then spread over 400-800 blocks
 // instead of 100-200 with the 2048 of rounds 1-3 (same-box A/B, round 4: 5.405 / 5.419 -> 5.384 / 5.385 ms and 5.506 /
 // 5.511 / 5.515 -> 5.481 / 5.477 / 5.490 ms per step; 256 and 1024 are in between)
+// (re-measured on the final tree of round 6, 1024 and 256 again within noise or behind: profiles/r04_bn_ew_items_ab.txt,
+// profiles/r06_knobs_remeasured_final_tree.txt)
+#define BN_EW_ITEMS 512
 static int ew_blocks(int64_t total) {
-  static const int per = getenv("MI_BN_EW_ITEMS") ? atoi(getenv("MI_BN_EW_ITEMS")) : 512;   // items per block (A/B knob)
-  const int64_t ipb = per >= 256 ? per : 512;
-  int64_t b = (total + ipb - 1) / ipb;
+  int64_t b = (total + BN_EW_ITEMS - 1) / BN_EW_ITEMS;
   if (b > 1024) b = 1024;
   if (b < 1) b = 1;
   return (int)b;
+}
+
+// what every pass requires of the channel count
+#define BN_REQUIRE_C(C, who) \
+  MI_REQUIRE((C) % 8 == 0 && (C) > 0 && (C) <= BN_MAXC, "%s: C %d (need C %% 8 == 0, 0 < C <= %d)", who, (int)(C), BN_MAXC)
+
+static int bn_fill_fwd(const mi_bn_job& b, BnFwdK* k, const char* who) {
+  MI_REQUIRE(b.y && b.scale && b.shift && b.a, "%s: null y / scale / shift / a", who);
+  MI_REQUIRE(!b.acc || (b.gamma && b.beta && b.mean && b.invstd && b.count > 0),
+             "%s: train mode needs gamma / beta / mean / invstd and count > 0", who);
+  BN_REQUIRE_C(b.C, who);
+  MI_REQUIRE(b.ldy % 8 == 0 && b.lda % 8 == 0 && (!b.res || b.ldres % 8 == 0), "%s: ld %% 8", who);
+  MI_REQUIRE(bn_al16(b.y) && bn_al16(b.a) && bn_al16(b.res), "%s: y / a / res not 16-byte aligned", who);
+  k->y = (const __bf16*)b.y; k->res = (const __bf16*)b.res; k->a = (__bf16*)b.a; k->acc = b.acc; k->gamma = b.gamma;
+  k->beta = b.beta; k->rmean = b.rmean; k->rvar = b.rvar; k->nbt = b.nbt; k->scale = b.scale; k->shift = b.shift;
+  k->mean = b.mean; k->invstd = b.invstd; k->ldy = b.ldy; k->ldres = b.ldres; k->lda = b.lda; k->C8 = b.C / 8;
+  k->nslots = bn_slots(b.nslots); k->npix = b.npix;
+  k->inv_count = b.acc ? 1.0 / (double)b.count : 0.0;   // (eval mode reads neither)
+  k->unbias = b.acc && b.count > 1 ? (double)b.count / (double)(b.count - 1) : 1.0;
+  k->eps = b.eps; k->momentum = b.momentum;
+  return MI_OK;
 }
 
 extern "C" int mi_bn_act_fwd(const void* y, int ldy, const double* stats_acc, int nslots, int64_t count, const float* gamma,
@@ -201,24 +194,13 @@ extern "C" int mi_bn_act_fwd(const void* y, int ldy, const double* stats_acc, in
                              int64_t* num_batches_tracked, float* scale, float* shift, float* mean, float* invstd,
                              const void* res, int ldres, void* a, int lda, int64_t npix, int C, int act,
                              mi_stream_t st) {
-  MI_REQUIRE(y && scale && shift && a, "bn_act_fwd: null");
-  MI_REQUIRE(!stats_acc || (gamma && beta && mean && invstd && count > 0), "bn_act_fwd: train mode needs gamma/beta/mean/invstd");
-  MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_act_fwd: C %d (need C %% 8 == 0, C <= %d)", C, BN_MAXC);
-  MI_REQUIRE(ldy % 8 == 0 && lda % 8 == 0 && (!res || ldres % 8 == 0), "bn_act_fwd: ld %% 8");
-  MI_REQUIRE(((uintptr_t)y % 16) == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)res % 16) == 0, "bn_act_fwd: align");
+  mi_bn_job b = bn_job(npix, C, nslots, act);
+  b.y = y; b.ldy = ldy; b.acc = (double*)stats_acc; b.count = count; b.gamma = gamma; b.beta = beta; b.eps = eps;
+  b.momentum = momentum; b.rmean = running_mean; b.rvar = running_var; b.nbt = num_batches_tracked; b.scale = scale;
+  b.shift = shift; b.mean = mean; b.invstd = invstd; b.res = res; b.ldres = ldres; b.a = a; b.lda = lda;
   BnFwdK k;
-  k.y = (const __bf16*)y; k.res = (const __bf16*)res; k.a = (__bf16*)a; k.acc = stats_acc; k.gamma = gamma;
-  k.beta = beta; k.rmean = running_mean; k.rvar = running_var; k.nbt = num_batches_tracked; k.scale = scale;
-  k.shift = shift; k.mean = mean; k.invstd = invstd; k.ldy = ldy; k.ldres = ldres; k.lda = lda; k.C8 = C / 8;
-  k.npix = npix; k.inv_count = count > 0 ? 1.0 / (double)count : 0.0;
-  k.unbias = count > 1 ? (double)count / (double)(count - 1) : 1.0;
-  k.eps = eps; k.momentum = momentum;
-  k.nslots = (nslots >= 1 && nslots <= MI_BN_SLOTS) ? nslots : MI_BN_SLOTS;
-  const int64_t total = npix * (C / 8);
-  if (act)
-    hipLaunchKernelGGL(bn_act_fwd_kernel<1>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)st, k);
-  else
-    hipLaunchKernelGGL(bn_act_fwd_kernel<0>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)st, k);
+  if (int rc = bn_fill_fwd(b, &k, "bn_act_fwd")) return rc;
+  BN_LAUNCH(bn_act_fwd_kernel, act, ew_blocks(npix * (C / 8)), st, k);
   MI_CHECK_LAUNCH("bn_act_fwd");
   return MI_OK;
 }
@@ -252,14 +234,14 @@ __device__ __forceinline__ void bn_bwd_reduce_body(PK& p, const int bid, const i
   const int PL = 256 / C8;                       // pixel lanes; threads beyond PL * C8 only take part in the barriers
   const bool active = tid < PL * C8;
   const int c8 = tid % C8, pl = active ? tid / C8 : 0;
-  float sc[8], sh[8], mu[8], is[8], s1[8], s2[8];
+  float sc[8], sh[8], mu[8], is[8], s[2][8];   // s: (sum dz, sum dz * xhat)
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     sc[e] = p.scale[c8 * 8 + e];
     sh[e] = p.shift[c8 * 8 + e];
     mu[e] = p.mean[c8 * 8 + e];
     is[e] = p.invstd[c8 * 8 + e];
-    s1[e] = s2[e] = 0.f;
+    s[0][e] = s[1][e] = 0.f;
   }
   const int64_t pstride = (int64_t)nb * PL;
   for (int64_t pix0 = active ? (int64_t)bid * PL + pl : p.npix; pix0 < p.npix; pix0 += 4 * pstride) {
@@ -280,29 +262,13 @@ __device__ __forceinline__ void bn_bwd_reduce_body(PK& p, const int bid, const i
         const float yy = (float)yv[u][e];
         const float z = yy * sc[e] + sh[e];
         const float dz = (float)dv[u][e] * act_grad(z, ACT);
-        s1[e] += dz;
-        s2[e] += dz * ((yy - mu[e]) * is[e]);
+        s[0][e] += dz;
+        s[1][e] += dz * ((yy - mu[e]) * is[e]);
       }
     }
   }
-  // red[pl][c8][16]
-  if (active) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(pl * C8 + c8) * 16 + e] = s1[e];
-      red[(pl * C8 + c8) * 16 + 8 + e] = s2[e];
-    }
-  }
-  __syncthreads();
-  const int nout = C8 * 16, C = C8 * 8;
-  double* slot = p.dacc + (size_t)(bid % p.nslots) * BN_ACC_C(C) * 2;
-  for (int j = tid; j < nout; j += 256) {
-    float acc = 0.f;
-    for (int q = 0; q < PL; ++q) acc += red[q * nout + j];
-    const int cc8 = j / 16, v = j % 16;
-    const int c = cc8 * 8 + (v & 7), which = v >> 3;
-    atomicAdd(slot + c * 2 + which, (double)acc);
-  }
+  double* slot = p.dacc + (size_t)(bid % p.nslots) * BN_ACC_C(C8 * 8) * 2;
+  bn_block_sums<2>(red, s, C8, PL, active, pl, c8, slot, nullptr);
 }
 
 template <int ACT>
@@ -319,21 +285,36 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_group_kernel(const BnRedK* 
   bn_bwd_reduce_body<ACT, KC4>(*pj, (int)blockIdx.x - starts[j], starts[j + 1] - starts[j]);
 }
 
+// what all three backward kinds require (a job's `acc` holds their dacc); apply: and what apply and fused add to it
+static int bn_check_bwd(const mi_bn_job& b, bool apply, const char* who) {
+  MI_REQUIRE(b.da && b.y && b.scale && b.shift && b.mean && b.invstd && b.acc, "%s: null da / y / scale / shift / mean / invstd / dacc", who);
+  BN_REQUIRE_C(b.C, who);
+  MI_REQUIRE(b.ldda % 8 == 0 && b.ldy % 8 == 0, "%s: ldda / ldy %% 8", who);
+  MI_REQUIRE(bn_al16(b.da) && bn_al16(b.y), "%s: da / y not 16-byte aligned", who);
+  if (!apply) return MI_OK;
+  MI_REQUIRE(b.gamma && b.dy && b.count > 0, "%s: null gamma / dy or count <= 0", who);
+  MI_REQUIRE(b.lddy % 8 == 0 && (!b.dres || b.lddres % 8 == 0), "%s: lddy / lddres %% 8", who);
+  MI_REQUIRE(bn_al16(b.dy) && bn_al16(b.dres), "%s: dy / dres not 16-byte aligned", who);
+  return MI_OK;
+}
+static int bn_fill_red(const mi_bn_job& b, BnRedK* k, const char* who) {
+  if (int rc = bn_check_bwd(b, false, who)) return rc;
+  MI_REQUIRE(b.nblk > 0, "%s: nblk %d", who, b.nblk);
+  k->da = (const __bf16*)b.da; k->y = (const __bf16*)b.y; k->scale = b.scale; k->shift = b.shift; k->mean = b.mean;
+  k->invstd = b.invstd; k->dacc = b.acc; k->ldda = b.ldda; k->ldy = b.ldy; k->nslots = bn_slots(b.nslots); k->C8 = b.C / 8;
+  k->npix = b.npix;
+  return MI_OK;
+}
+
 extern "C" int mi_bn_act_bwd_reduce(const void* da, int ldda, const void* y, int ldy, const float* scale,
                                     const float* shift, const float* mean, const float* invstd, double* dacc,
                                     int nslots, int nblk, int64_t npix, int C, int act, mi_stream_t st) {
-  if (nslots < 1 || nslots > MI_BN_SLOTS) nslots = MI_BN_SLOTS;
-  MI_REQUIRE(da && y && scale && shift && mean && invstd && dacc, "bn_bwd_reduce: null");
-  MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_bwd_reduce: C %d (need C %% 8 == 0, C <= %d)", C, BN_MAXC);
-  MI_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && nblk > 0, "bn_bwd_reduce: ld");
-  MI_REQUIRE(bn_al16(da) && bn_al16(y), "bn_bwd_reduce: align");
+  mi_bn_job b = bn_job(npix, C, nslots, act);
+  b.da = da; b.ldda = ldda; b.y = y; b.ldy = ldy; b.scale = (float*)scale; b.shift = (float*)shift; b.mean = (float*)mean;
+  b.invstd = (float*)invstd; b.acc = dacc; b.nblk = nblk;
   BnRedK k;
-  k.da = (const __bf16*)da; k.y = (const __bf16*)y; k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd;
-  k.dacc = dacc; k.ldda = ldda; k.ldy = ldy; k.nslots = nslots; k.C8 = C / 8; k.npix = npix;
-  if (act)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(nblk), dim3(256), 0, (hipStream_t)st, k);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<0>, dim3(nblk), dim3(256), 0, (hipStream_t)st, k);
+  if (int rc = bn_fill_red(b, &k, "bn_bwd_reduce")) return rc;
+  BN_LAUNCH(bn_bwd_reduce_kernel, act, nblk, st, k);
   MI_CHECK_LAUNCH("bn_bwd_reduce");
   return MI_OK;
 }
@@ -361,25 +342,8 @@ struct BnBwdK {
 template <int ACT, class PK>
 __device__ __forceinline__ void bn_bwd_apply_body(PK& p, const int bid, const int nb) {
   __shared__ float s_c1[BN_MAXC], s_c2[BN_MAXC];
-  const int C8 = p.C8, C = C8 * 8, CA = BN_ACC_C(C);
-  for (int c = threadIdx.x; c < C; c += 256) {
-    f64x2 v[MI_BN_SLOTS];
-#pragma unroll
-    for (int k = 0; k < MI_BN_SLOTS; ++k)
-      v[k] = k < p.nslots ? *(const f64x2*)(p.dacc + ((size_t)k * CA + c) * 2) : f64x2{0.0, 0.0};
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < MI_BN_SLOTS; ++k) {
-      s1 += v[k][0];
-      s2 += v[k][1];
-    }
-    s_c1[c] = (float)(s1 * p.inv_count);
-    s_c2[c] = (float)(s2 * p.inv_count);
-    if (bid == 0) {
-      if (p.dbeta) p.dbeta[c] = (float)s1;
-      if (p.dgamma) p.dgamma[c] = (float)s2;
-    }
-  }
+  const int C8 = p.C8;
+  bn_bwd_prologue(p, C8 * 8, bid, s_c1, s_c2);
   __syncthreads();
   const int64_t total = p.npix * C8;
   const int TPB = (256 / C8) * C8;
@@ -455,27 +419,39 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(const BnBwdK* _
   bn_bwd_apply_body<ACT, KC4>(*pj, (int)blockIdx.x - starts[j], starts[j + 1] - starts[j]);
 }
 
+// the arguments mi_bn_act_bwd_apply and mi_bn_act_bwd_fused share, as a job
+static mi_bn_job bn_bwd_job(const void* da, int ldda, const void* y, int ldy, const float* scale, const float* shift,
+                            const float* mean, const float* invstd, const float* gamma, const double* dacc, int nslots,
+                            int64_t count, float* dgamma, float* dbeta, void* dy, int lddy, void* dres, int lddres,
+                            int dres_accum, int64_t npix, int C, int act) {
+  mi_bn_job b = bn_job(npix, C, nslots, act);
+  b.da = da; b.ldda = ldda; b.y = y; b.ldy = ldy; b.scale = (float*)scale; b.shift = (float*)shift; b.mean = (float*)mean;
+  b.invstd = (float*)invstd; b.gamma = gamma; b.acc = (double*)dacc; b.count = count; b.dgamma = dgamma; b.dbeta = dbeta;
+  b.dy = dy; b.lddy = lddy; b.dres = dres; b.lddres = lddres; b.dres_accum = dres_accum;
+  return b;
+}
+// K: BnBwdK or BnFusK, which begins with the same fields
+template <class K>
+static int bn_fill_apply(const mi_bn_job& b, K* k, const char* who) {
+  if (int rc = bn_check_bwd(b, true, who)) return rc;
+  k->da = (const __bf16*)b.da; k->y = (const __bf16*)b.y; k->dy = (__bf16*)b.dy; k->dres = (__bf16*)b.dres; k->dacc = b.acc;
+  k->scale = b.scale; k->shift = b.shift; k->mean = b.mean; k->invstd = b.invstd; k->gamma = b.gamma; k->dgamma = b.dgamma;
+  k->dbeta = b.dbeta; k->ldda = b.ldda; k->ldy = b.ldy; k->lddy = b.lddy; k->lddres = b.lddres; k->dres_accum = b.dres_accum;
+  k->C8 = b.C / 8; k->nslots = bn_slots(b.nslots); k->npix = b.npix; k->inv_count = 1.0 / (double)b.count;
+  return MI_OK;
+}
+
 extern "C" int mi_bn_act_bwd_apply(const void* da, int ldda, const void* y, int ldy, const float* scale,
                                    const float* shift, const float* mean, const float* invstd, const float* gamma,
                                    const double* dacc, int nslots, int64_t count, float* dgamma, float* dbeta, void* dy,
                                    int lddy,
                                    void* dres, int lddres, int dres_accum, int64_t npix, int C, int act,
                                    mi_stream_t st) {
-  MI_REQUIRE(da && y && scale && shift && mean && invstd && gamma && dacc && dy && count > 0, "bn_bwd_apply: null");
-  MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_bwd_apply: C %d", C);
-  MI_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && (!dres || lddres % 8 == 0), "bn_bwd_apply: ld");
-  MI_REQUIRE(bn_al16(da) && bn_al16(y) && bn_al16(dy) && bn_al16(dres), "bn_bwd_apply: align");
+  const mi_bn_job b = bn_bwd_job(da, ldda, y, ldy, scale, shift, mean, invstd, gamma, dacc, nslots, count, dgamma, dbeta, dy,
+                                 lddy, dres, lddres, dres_accum, npix, C, act);
   BnBwdK k;
-  k.da = (const __bf16*)da; k.y = (const __bf16*)y; k.dy = (__bf16*)dy; k.dres = (__bf16*)dres; k.dacc = dacc;
-  k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd; k.gamma = gamma; k.dgamma = dgamma;
-  k.dbeta = dbeta; k.ldda = ldda; k.ldy = ldy; k.lddy = lddy; k.lddres = lddres; k.dres_accum = dres_accum;
-  k.C8 = C / 8; k.npix = npix; k.inv_count = 1.0 / (double)count;
-  k.nslots = (nslots >= 1 && nslots <= MI_BN_SLOTS) ? nslots : MI_BN_SLOTS;
-  const int64_t total = npix * (C / 8);
-  if (act)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)st, k);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<0>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)st, k);
+  if (int rc = bn_fill_apply(b, &k, "bn_bwd_apply")) return rc;
+  BN_LAUNCH(bn_bwd_apply_kernel, act, ew_blocks(npix * (C / 8)), st, k);
   MI_CHECK_LAUNCH("bn_bwd_apply");
   return MI_OK;
 }
@@ -501,20 +477,20 @@ struct BnFusK {
   const float* gamma;
   float* dgamma;
   float* dbeta;
-  int ldda, ldy, lddy, lddres, dres_accum, C8, nslots, rsv_;   // rsv_ 1: round 4's form of phase 2 (every block reads every slot; A/B only)
+  int ldda, ldy, lddy, lddres, dres_accum, C8, nslots, pad_;
   int64_t npix;
   double inv_count;
 };
 
-// MODE 0: da and y stay in registers as loaded (bf16, 8 VGPRs per item, 16 items); phase 2 recomputes the activation
-//         gradient.  MODE 1: dz stays in fp32 registers and y in LDS (14 items, 72 KB per block); phase 2 is 5 flops per
-//         element.
-template <int ACT, int MODE, class PK>
+// The first R = 14 items of a thread stay on chip: dz in fp32 registers and y in LDS (72 KB per block), so phase 2 is 5 flops
+// per element.  (The form that kept da and y in registers as loaded, 16 items, and recomputed the activation gradient in
+// phase 2 lost: profiles/bn_fused_mode_ab.txt.)
+template <int ACT, class PK>
 __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const int nb) {
-  constexpr int R = MODE ? 14 : 16;
-  // LDS: 16 KB block reduction scratch (re-used for the finished sums after the barrier) + (MODE 1) the retained y items
+  constexpr int R = 14;
+  // LDS: 16 KB block reduction scratch (re-used for the finished sums after the barrier) + the retained y items
   __shared__ float red[256 * 16];
-  __shared__ bf16x8 ylds[MODE ? R : 1][MODE ? 256 : 1];
+  __shared__ bf16x8 ylds[R][256];
   float* s_c1 = red;
   float* s_c2 = red + BN_MAXC;
   const int tid = threadIdx.x;
@@ -523,8 +499,7 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   const bool active = tid < TPB;
   const int c8 = tid % C8, pl = active ? tid / C8 : 0;
   unsigned gen0 = 0;   // thread 0 only
-  if (tid == 0)
-    gen0 = __hip_atomic_load(bn_bar_gen(p.bar, bid % (nb < BN_BAR_G ? nb : BN_BAR_G)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) gen0 = __hip_atomic_load(bn_bar_gen(p.bar, bn_bar_group(bid, nb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // item = (pixel, channel group); TPB % C8 == 0: the thread's pixels are pix0 + k * pstep.  Addresses are a uniform
   // 64-bit base (+ k * uniform step) plus ONE 32-bit per-thread byte offset per tensor (host checks the 4 GB bound), so
   // the retained items cost no address registers.
@@ -553,10 +528,10 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
       *rp = d;
     }
   };
-  bf16x8 dv[R], yv[R];          // MODE 0: live across the barrier
-  float dzr[MODE ? R : 1][8];   // MODE 1
-  float s1[8], s2[8];
+  float dzr[R][8];   // live across the barrier
+  float s[2][8];     // (sum dz, sum dz * xhat)
   {
+    bf16x8 dv[R], yv[R];
 #pragma unroll
     for (int u = 0; u < R; ++u) {
       if (u < nmine) {
@@ -571,21 +546,21 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
       sh[e] = p.shift[c8 * 8 + e];
       mu[e] = p.mean[c8 * 8 + e];
       is[e] = p.invstd[c8 * 8 + e];
-      s1[e] = s2[e] = 0.f;
+      s[0][e] = s[1][e] = 0.f;
     }
 #pragma unroll
     for (int u = 0; u < R; ++u) {
       if (u < nmine) {
         pass_res(u, dv[u]);
-        if (MODE) ylds[MODE ? u : 0][MODE ? tid : 0] = yv[u];
+        ylds[u][tid] = yv[u];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float yy = (float)yv[u][e];
           const float z = yy * sc[e] + sh[e];
           const float dz = (float)dv[u][e] * act_grad(z, ACT);
-          if (MODE) dzr[MODE ? u : 0][e] = dz;
-          s1[e] += dz;
-          s2[e] += dz * ((yy - mu[e]) * is[e]);
+          dzr[u][e] = dz;
+          s[0][e] += dz;
+          s[1][e] += dz * ((yy - mu[e]) * is[e]);
         }
       }
     }
@@ -608,40 +583,22 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
           const float yy = (float)y4[u][e];
           const float z = yy * sc[e] + sh[e];
           const float dz = (float)d4[u][e] * act_grad(z, ACT);
-          s1[e] += dz;
-          s2[e] += dz * ((yy - mu[e]) * is[e]);
+          s[0][e] += dz;
+          s[1][e] += dz * ((yy - mu[e]) * is[e]);
         }
       }
     }
   }
-  if (active) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(pl * C8 + c8) * 16 + e] = s1[e];
-      red[(pl * C8 + c8) * 16 + 8 + e] = s2[e];
-    }
-  }
-  __syncthreads();
-  {
-    const int nout = C8 * 16;
-    double* slot = p.dacc + (size_t)(bid % p.nslots) * CA * 2;
-    for (int j = tid; j < nout; j += 256) {
-      float acc = 0.f;
-      for (int q = 0; q < PL; ++q) acc += red[q * nout + j];
-      const int cc8 = j / 16, v = j % 16;
-      atomicAdd(slot + (cc8 * 8 + (v & 7)) * 2 + (v >> 3), (double)acc);
-    }
-  }
+  bn_block_sums<2>(red, s, C8, PL, active, pl, c8, p.dacc + (size_t)(bid % p.nslots) * CA * 2, nullptr);
   __shared__ int s_gave_up, s_last;
   // The grid barrier in two halves (conv_bn.h): the block that arrives last folds the nslots accumulator slots of every
   // channel into slot 0 (same fixed order as before: identical totals) and records dgamma / dbeta BEFORE it releases the
   // others, which then read two fp64 totals per channel.  Round 4 had EVERY block read every slot after the barrier:
   // C x nslots x 2 agent-scope 8-byte loads per block (they bypass the XCD's L2: one memory-side request each), 2 M requests
   // for a 256-channel layer on 512 blocks - measured on the same pattern in round 5's first conv prologue: ~9 us for
-  // C = 512 (profiles/r05_bn_bwd_last_arriver_ab.txt).
+  // C = 512 (profiles/r05_bn_bwd_last_arriver_ab.txt; that form is gone).
   bn_bar_arrive(p.bar, bid, nb, &s_gave_up, &s_last);   // (its leading __syncthreads also ends the reads of red[])
-  const bool legacy = p.rsv_ != 0;
-  if (s_last && !legacy) {
+  if (s_last) {
     for (int c = tid; c < C; c += 256) {
       double v1[MI_BN_SLOTS], v2[MI_BN_SLOTS];
 #pragma unroll
@@ -671,18 +628,8 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   const float poison = s_gave_up ? __builtin_nanf("") : 0.f;
   // ---- phase 2: the finished totals (agent-scope loads: written by a block of another XCD)
   for (int c = tid; c < C; c += 256) {
-    double t1 = __hip_atomic_load(p.dacc + (size_t)c * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    double t2 = __hip_atomic_load(p.dacc + (size_t)c * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (legacy) {   // (slot 0 still holds its own partial: add the others)
-      for (int k = 1; k < p.nslots; ++k) {
-        t1 += __hip_atomic_load(p.dacc + ((size_t)k * CA + c) * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t2 += __hip_atomic_load(p.dacc + ((size_t)k * CA + c) * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (bid == 0) {
-        if (p.dbeta) p.dbeta[c] = (float)t1 + poison;
-        if (p.dgamma) p.dgamma[c] = (float)t2 + poison;
-      }
-    }
+    const double t1 = __hip_atomic_load(p.dacc + (size_t)c * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double t2 = __hip_atomic_load(p.dacc + (size_t)c * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s_c1[c] = (float)(t1 * p.inv_count) + poison;
     s_c2[c] = (float)(t2 * p.inv_count) + poison;
   }
@@ -703,6 +650,20 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   char* dyb = (char*)p.dy;
   const unsigned ody = (unsigned)((pix0 * p.lddy + c8 * 8) * 2);
   const int64_t sdy = pstep * p.lddy * 2;
+#pragma unroll
+  for (int u = 0; u < R; ++u) {
+    if (u < nmine) {
+      const bf16x8 yk = ylds[u][tid];
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xh = ((float)yk[e] - mu[e]) * is[e];
+        o[e] = gi[e] * (dzr[u][e] - k1[e] - xh * k2[e]);
+      }
+      *(bf16x8*)(dyb + u * sdy + ody) = pack8(o);
+    }
+  }
+  // the streamed items beyond R: recomputed from (da, y), as bn_bwd_apply does
   auto full = [&](const int k, const bf16x8& d, const bf16x8& yy8) {
     float o[8];
 #pragma unroll
@@ -715,23 +676,6 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
     }
     *(bf16x8*)(dyb + k * sdy + ody) = pack8(o);
   };
-#pragma unroll
-  for (int u = 0; u < R; ++u) {
-    if (u < nmine) {
-      if (MODE) {
-        const bf16x8 yk = ylds[MODE ? u : 0][MODE ? tid : 0];
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xh = ((float)yk[e] - mu[e]) * is[e];
-          o[e] = gi[e] * (dzr[MODE ? u : 0][e] - k1[e] - xh * k2[e]);
-        }
-        *(bf16x8*)(dyb + u * sdy + ody) = pack8(o);
-      } else {
-        full(u, dv[u], yv[u]);
-      }
-    }
-  }
   for (int k0 = R; k0 < nmine; k0 += 2) {
     bf16x8 d2[2], y2[2];
 #pragma unroll
@@ -747,35 +691,17 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   }
 }
 
-template <int ACT, int MODE>
+template <int ACT>
 __global__ __launch_bounds__(256, 2) void bn_bwd_fused_kernel(const BnFusK p) {
-  bn_bwd_fused_body<ACT, MODE, const BnFusK>(p, blockIdx.x, gridDim.x);
+  bn_bwd_fused_body<ACT, const BnFusK>(p, blockIdx.x, gridDim.x);
 }
-template <int ACT, int MODE>
+template <int ACT>
 __global__ __launch_bounds__(256, 2) void bn_bwd_fused_group_kernel(const BnFusK* __restrict__ jobs,
                                                                     const int* __restrict__ starts, int njobs) {
   const int j = bn_group_job(starts, njobs);
   typedef const __attribute__((address_space(4))) BnFusK KC4;
   KC4* pj = (KC4*)(uintptr_t)(jobs + j);
-  bn_bwd_fused_body<ACT, MODE, KC4>(*pj, (int)blockIdx.x - starts[j], starts[j + 1] - starts[j]);
-}
-// MI_BN_BWD_LAST=0: the round-4 form of the phase between the two halves (A/B runs); read once
-static int bn_fused_every_block_reads() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MI_BN_BWD_LAST");
-    v = (e && atoi(e) == 0) ? 1 : 0;
-  }
-  return v;
-}
-static int bn_fused_mode() {
-  static int m = -1;
-  if (m < 0) {
-    const char* e = getenv("MI_BN_FUSED_MODE");
-    m = e ? atoi(e) : 1;
-    if (m != 0) m = 1;
-  }
-  return m;
+  bn_bwd_fused_body<ACT, KC4>(*pj, (int)blockIdx.x - starts[j], starts[j + 1] - starts[j]);
 }
 
 // number of 256-thread blocks of the fused kernel the GPU keeps resident at once (the grid barrier needs all of them)
@@ -789,13 +715,11 @@ static int bn_fused_capacity_hw() {
     (void)hipGetLastError();
     return 512;  // no device (host-side planning of a dry run): the MI355X figure, 256 CUs x 2
   }
-  // the grid size is shared by all four instantiations (MI_BN_FUSED_MODE, activation on / off) and their grouped forms: the
-  // one with the fewest resident blocks per CU bounds it (MODE 0 keeps 32 16-byte items in registers)
+  // the grid size is shared by both instantiations (activation on / off) and their grouped forms: the one with the fewest
+  // resident blocks per CU bounds it
   per = 2;
-  const void* variants[] = {(const void*)bn_bwd_fused_kernel<1, 1>, (const void*)bn_bwd_fused_kernel<1, 0>,
-                            (const void*)bn_bwd_fused_kernel<0, 1>, (const void*)bn_bwd_fused_kernel<0, 0>,
-                            (const void*)bn_bwd_fused_group_kernel<1, 1>, (const void*)bn_bwd_fused_group_kernel<1, 0>,
-                            (const void*)bn_bwd_fused_group_kernel<0, 1>, (const void*)bn_bwd_fused_group_kernel<0, 0>};
+  const void* variants[] = {(const void*)bn_bwd_fused_kernel<1>, (const void*)bn_bwd_fused_kernel<0>,
+                            (const void*)bn_bwd_fused_group_kernel<1>, (const void*)bn_bwd_fused_group_kernel<0>};
   for (const void* fn : variants) {
     int q = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn, 256, 0) != hipSuccess || q < 1) q = 1;
@@ -818,38 +742,36 @@ static bool bn_fused_fits(int64_t npix, int ldda, int ldy, int lddy, int lddres)
   if (lddres > ld) ld = lddres;
   return npix * ld * 2 < (1LL << 32) - 4096;   // 32-bit per-thread byte offsets
 }
+// at least ~4 items per thread (the barrier costs one atomic round trip per block), never more than `cap` blocks (3 items:
+// 5.282 / 5.286 against 5.283 / 5.276 ms per step, profiles/r06_knobs_remeasured_final_tree.txt)
+#define BN_FUSED_ITEMS 4
 static int bn_fused_blocks(int64_t npix, int C8, int cap) {
-  // at least ~4 items per thread (the barrier costs one atomic round trip per block), never more than `cap` blocks
   const int64_t TPB = (256 / C8) * C8;
-  static const int ipt_e = getenv("MI_BN_FUSED_ITEMS") ? atoi(getenv("MI_BN_FUSED_ITEMS")) : 4;   // A/B knob
-  const int64_t ipt = ipt_e >= 1 && ipt_e <= 16 ? ipt_e : 4;
-  int64_t b = (npix * C8 + TPB * ipt - 1) / (TPB * ipt);
+  int64_t b = (npix * C8 + TPB * BN_FUSED_ITEMS - 1) / (TPB * BN_FUSED_ITEMS);
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
+}
+
+static int bn_fill_fused(const mi_bn_job& b, BnFusK* k, const char* who) {
+  if (int rc = bn_fill_apply(b, k, who)) return rc;
+  MI_REQUIRE(b.bar != nullptr, "%s: null barrier words", who);
+  MI_REQUIRE(bn_fused_fits(b.npix, b.ldda, b.ldy, b.lddy, b.dres ? b.lddres : 0), "%s: tensors beyond 4 GB (use reduce + apply)", who);
+  k->bar = b.bar;
+  k->pad_ = 0;
+  return MI_OK;
 }
 
 extern "C" int mi_bn_act_bwd_fused(const void* da, int ldda, const void* y, int ldy, const float* scale, const float* shift,
                                    const float* mean, const float* invstd, const float* gamma, double* dacc, int nslots,
                                    int64_t count, float* dgamma, float* dbeta, void* dy, int lddy, void* dres, int lddres,
                                    int dres_accum, int64_t npix, int C, int act, uint32_t* barrier_words, mi_stream_t st) {
-  MI_REQUIRE(da && y && scale && shift && mean && invstd && gamma && dacc && dy && barrier_words && count > 0, "bn_bwd_fused: null");
-  MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC, "bn_bwd_fused: C %d", C);
-  MI_REQUIRE(ldda % 8 == 0 && ldy % 8 == 0 && lddy % 8 == 0 && (!dres || lddres % 8 == 0), "bn_bwd_fused: ld");
-  MI_REQUIRE(bn_al16(da) && bn_al16(y) && bn_al16(dy) && bn_al16(dres), "bn_bwd_fused: align");
-  MI_REQUIRE(bn_fused_fits(npix, ldda, ldy, lddy, dres ? lddres : 0), "bn_bwd_fused: tensors beyond 4 GB (use reduce + apply)");
+  mi_bn_job b = bn_bwd_job(da, ldda, y, ldy, scale, shift, mean, invstd, gamma, dacc, nslots, count, dgamma, dbeta, dy, lddy,
+                           dres, lddres, dres_accum, npix, C, act);
+  b.bar = barrier_words;
   BnFusK k;
-  k.da = (const __bf16*)da; k.y = (const __bf16*)y; k.dy = (__bf16*)dy; k.dres = (__bf16*)dres; k.dacc = dacc;
-  k.bar = barrier_words; k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd; k.gamma = gamma;
-  k.dgamma = dgamma; k.dbeta = dbeta; k.ldda = ldda; k.ldy = ldy; k.lddy = lddy; k.lddres = lddres;
-  k.dres_accum = dres_accum; k.C8 = C / 8; k.rsv_ = bn_fused_every_block_reads(); k.npix = npix; k.inv_count = 1.0 / (double)count;
-  k.nslots = (nslots >= 1 && nslots <= MI_BN_SLOTS) ? nslots : MI_BN_SLOTS;
-  const int nb = bn_fused_blocks(npix, C / 8, bn_fused_capacity());
-  const int mode = bn_fused_mode();
-  if (act && mode) hipLaunchKernelGGL((bn_bwd_fused_kernel<1, 1>), dim3(nb), dim3(256), 0, (hipStream_t)st, k);
-  else if (act) hipLaunchKernelGGL((bn_bwd_fused_kernel<1, 0>), dim3(nb), dim3(256), 0, (hipStream_t)st, k);
-  else if (mode) hipLaunchKernelGGL((bn_bwd_fused_kernel<0, 1>), dim3(nb), dim3(256), 0, (hipStream_t)st, k);
-  else hipLaunchKernelGGL((bn_bwd_fused_kernel<0, 0>), dim3(nb), dim3(256), 0, (hipStream_t)st, k);
+  if (int rc = bn_fill_fused(b, &k, "bn_bwd_fused")) return rc;
+  BN_LAUNCH(bn_bwd_fused_kernel, act, bn_fused_blocks(npix, C / 8, bn_fused_capacity()), st, k);
   MI_CHECK_LAUNCH("bn_bwd_fused");
   return MI_OK;
 }
@@ -871,69 +793,25 @@ extern "C" int mi_bn_group_plan(int kind, const mi_bn_job* jobs, int n, void* ta
   if (kind == 3) {
     MI_REQUIRE(n <= cap, "bn_group_plan: more fused jobs than resident blocks");
     for (int j = 0; j < n; ++j)
-      if (jobs[j].C > 0 && jobs[j].C % 8 == 0) want += bn_fused_blocks(jobs[j].npix, jobs[j].C / 8, cap);
+      if (jobs[j].C > 0 && jobs[j].C % 8 == 0 && jobs[j].C <= BN_MAXC) want += bn_fused_blocks(jobs[j].npix, jobs[j].C / 8, cap);
   }
   for (int j = 0; j < n; ++j) {
     const mi_bn_job& b = jobs[j];
-    const int C = b.C;
-    MI_REQUIRE(C % 8 == 0 && C > 0 && C <= BN_MAXC && b.npix > 0, "bn_group_plan: job %d C %d", j, C);
+    char who[32];
+    snprintf(who, sizeof(who), "bn_group_plan: job %d", j);
+    MI_REQUIRE(b.npix > 0, "%s: npix %lld is not positive", who, (long long)b.npix);
     MI_REQUIRE(b.act == jobs[0].act, "bn_group_plan: jobs must agree on the activation");
-    const int nslots = (b.nslots >= 1 && b.nslots <= MI_BN_SLOTS) ? b.nslots : MI_BN_SLOTS;
-    const int64_t total = b.npix * (C / 8);
-    int nb = ew_blocks(total);
-    // what the single-layer entry points require of the tensors a kind touches (the others may hold anything)
-    if (kind == 0)
-      MI_REQUIRE(bn_al16(b.y) && bn_al16(b.a) && bn_al16(b.res), "bn_group_plan: job %d align", j);
-    else
-      MI_REQUIRE(b.ldda % 8 == 0 && b.ldy % 8 == 0 && bn_al16(b.da) && bn_al16(b.y), "bn_group_plan: job %d ld / align", j);
-    if (kind >= 2)
-      MI_REQUIRE(b.lddy % 8 == 0 && (!b.dres || b.lddres % 8 == 0) && bn_al16(b.dy) && bn_al16(b.dres),
-                 "bn_group_plan: job %d ld / align", j);
-    if (kind == 0) {
-      MI_REQUIRE(b.y && b.a && b.scale && b.shift && b.ldy % 8 == 0 && b.lda % 8 == 0 && (!b.res || b.ldres % 8 == 0),
-                 "bn_group_plan: fwd job %d", j);
-      BnFwdK& k = kf[j];
-      k.y = (const __bf16*)b.y; k.res = (const __bf16*)b.res; k.a = (__bf16*)b.a; k.acc = b.acc; k.gamma = b.gamma;
-      k.beta = b.beta; k.rmean = b.rmean; k.rvar = b.rvar; k.nbt = b.nbt; k.scale = b.scale; k.shift = b.shift;
-      k.mean = b.mean; k.invstd = b.invstd; k.ldy = b.ldy; k.ldres = b.ldres; k.lda = b.lda; k.C8 = C / 8;
-      k.npix = b.npix; k.nslots = nslots;
-      if (b.acc) {
-        MI_REQUIRE(b.gamma && b.beta && b.mean && b.invstd && b.count > 0, "bn_group_plan: train-mode fwd job %d", j);
-        k.inv_count = 1.0 / (double)b.count;
-        k.unbias = b.count > 1 ? (double)b.count / (double)(b.count - 1) : 1.0;
-      } else {
-        k.inv_count = 0.0; k.unbias = 1.0;
-      }
-      k.eps = b.eps; k.momentum = b.momentum;
-    } else if (kind == 1) {
-      MI_REQUIRE(b.da && b.y && b.scale && b.shift && b.mean && b.invstd && b.acc && b.nblk > 0, "bn_group_plan: reduce job %d", j);
-      BnRedK& k = kr[j];
-      k.da = (const __bf16*)b.da; k.y = (const __bf16*)b.y; k.scale = b.scale; k.shift = b.shift; k.mean = b.mean;
-      k.invstd = b.invstd; k.dacc = b.acc; k.ldda = b.ldda; k.ldy = b.ldy; k.nslots = nslots; k.C8 = C / 8; k.npix = b.npix;
-      nb = b.nblk;
-    } else if (kind == 3) {
-      MI_REQUIRE(b.da && b.y && b.scale && b.shift && b.mean && b.invstd && b.gamma && b.acc && b.dy && b.bar && b.count > 0,
-                 "bn_group_plan: fused job %d", j);
-      MI_REQUIRE(bn_fused_fits(b.npix, b.ldda, b.ldy, b.lddy, b.dres ? b.lddres : 0), "bn_group_plan: fused job %d beyond 4 GB", j);
-      BnFusK& k = ku[j];
-      k.da = (const __bf16*)b.da; k.y = (const __bf16*)b.y; k.dy = (__bf16*)b.dy; k.dres = (__bf16*)b.dres; k.dacc = b.acc;
-      k.bar = b.bar; k.scale = b.scale; k.shift = b.shift; k.mean = b.mean; k.invstd = b.invstd; k.gamma = b.gamma;
-      k.dgamma = b.dgamma; k.dbeta = b.dbeta; k.ldda = b.ldda; k.ldy = b.ldy; k.lddy = b.lddy; k.lddres = b.lddres;
-      k.dres_accum = b.dres_accum; k.C8 = C / 8; k.rsv_ = bn_fused_every_block_reads(); k.npix = b.npix; k.inv_count = 1.0 / (double)b.count;
-      k.nslots = nslots;
-      nb = bn_fused_blocks(b.npix, C / 8, cap);
+    // the checks of the single-layer entry point of this kind, on the tensors the kind touches (the others may hold anything)
+    if (int rc = kind == 0 ? bn_fill_fwd(b, &kf[j], who) : kind == 1 ? bn_fill_red(b, &kr[j], who)
+                 : kind == 2 ? bn_fill_apply(b, &ka[j], who) : bn_fill_fused(b, &ku[j], who))
+      return rc;
+    int nb = kind == 1 ? b.nblk : ew_blocks(b.npix * (b.C / 8));
+    if (kind == 3) {
+      nb = bn_fused_blocks(b.npix, b.C / 8, cap);
       if (want > cap) {
         nb = (int)((int64_t)nb * (cap - n) / want);   // sum <= cap - n, + 1 each below
         nb += 1;
       }
-    } else {
-      MI_REQUIRE(b.da && b.y && b.scale && b.shift && b.mean && b.invstd && b.gamma && b.acc && b.dy && b.count > 0,
-                 "bn_group_plan: apply job %d", j);
-      BnBwdK& k = ka[j];
-      k.da = (const __bf16*)b.da; k.y = (const __bf16*)b.y; k.dy = (__bf16*)b.dy; k.dres = (__bf16*)b.dres; k.dacc = b.acc;
-      k.scale = b.scale; k.shift = b.shift; k.mean = b.mean; k.invstd = b.invstd; k.gamma = b.gamma; k.dgamma = b.dgamma;
-      k.dbeta = b.dbeta; k.ldda = b.ldda; k.ldy = b.ldy; k.lddy = b.lddy; k.lddres = b.lddres; k.dres_accum = b.dres_accum;
-      k.C8 = C / 8; k.npix = b.npix; k.inv_count = 1.0 / (double)b.count; k.nslots = nslots;
     }
     starts[j + 1] = starts[j] + nb;
   }
@@ -953,25 +831,15 @@ extern "C" int mi_bn_group_plan(int kind, const mi_bn_job* jobs, int n, void* ta
 extern "C" int mi_bn_group_run(const mi_bn_group* m, const void* table_dev, mi_stream_t st) {
   MI_REQUIRE(m && table_dev && m->njobs >= 1 && m->nblocks >= 1, "bn_group_run: args");
   const int* starts = (const int*)((const char*)table_dev + m->starts_off);
-  hipStream_t s = (hipStream_t)st;
-  const dim3 g((unsigned)m->nblocks), b(256);
   if (m->kind == 0) {
-    if (m->act) hipLaunchKernelGGL(bn_act_fwd_group_kernel<1>, g, b, 0, s, (const BnFwdK*)table_dev, starts, m->njobs);
-    else hipLaunchKernelGGL(bn_act_fwd_group_kernel<0>, g, b, 0, s, (const BnFwdK*)table_dev, starts, m->njobs);
+    BN_LAUNCH(bn_act_fwd_group_kernel, m->act, m->nblocks, st, (const BnFwdK*)table_dev, starts, m->njobs);
   } else if (m->kind == 1) {
-    if (m->act) hipLaunchKernelGGL(bn_bwd_reduce_group_kernel<1>, g, b, 0, s, (const BnRedK*)table_dev, starts, m->njobs);
-    else hipLaunchKernelGGL(bn_bwd_reduce_group_kernel<0>, g, b, 0, s, (const BnRedK*)table_dev, starts, m->njobs);
+    BN_LAUNCH(bn_bwd_reduce_group_kernel, m->act, m->nblocks, st, (const BnRedK*)table_dev, starts, m->njobs);
   } else if (m->kind == 2) {
-    if (m->act) hipLaunchKernelGGL(bn_bwd_apply_group_kernel<1>, g, b, 0, s, (const BnBwdK*)table_dev, starts, m->njobs);
-    else hipLaunchKernelGGL(bn_bwd_apply_group_kernel<0>, g, b, 0, s, (const BnBwdK*)table_dev, starts, m->njobs);
+    BN_LAUNCH(bn_bwd_apply_group_kernel, m->act, m->nblocks, st, (const BnBwdK*)table_dev, starts, m->njobs);
   } else {
     MI_REQUIRE(m->nblocks <= bn_fused_capacity(), "bn_group_run: fused launch of %d blocks exceeds the resident capacity", m->nblocks);
-    const int mode = bn_fused_mode();
-    const BnFusK* jt = (const BnFusK*)table_dev;
-    if (m->act && mode) hipLaunchKernelGGL((bn_bwd_fused_group_kernel<1, 1>), g, b, 0, s, jt, starts, m->njobs);
-    else if (m->act) hipLaunchKernelGGL((bn_bwd_fused_group_kernel<1, 0>), g, b, 0, s, jt, starts, m->njobs);
-    else if (mode) hipLaunchKernelGGL((bn_bwd_fused_group_kernel<0, 1>), g, b, 0, s, jt, starts, m->njobs);
-    else hipLaunchKernelGGL((bn_bwd_fused_group_kernel<0, 0>), g, b, 0, s, jt, starts, m->njobs);
+    BN_LAUNCH(bn_bwd_fused_group_kernel, m->act, m->nblocks, st, (const BnFusK*)table_dev, starts, m->njobs);
   }
   MI_CHECK_LAUNCH("bn_group");
   return MI_OK;

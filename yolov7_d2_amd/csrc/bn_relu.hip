@@ -24,11 +24,9 @@
 #include <string.h>
 #include <stdlib.h>
 #include "common.h"
+#include "bn_common.h"
 
-#define BR_MAXC 2048
-#define BR_ACC_C(C) (((C) + 31) / 32 * 32)
 #define BR_MAX_BLOCKS 1024
-static inline bool br_al16(const void* p) { return ((uintptr_t)p % 16) == 0; }   // NULL (an absent optional tensor) passes
 
 // FORM: 0 one norm, 1 two norms, 2 one norm + plain residual
 struct BrNormFwd {
@@ -55,55 +53,13 @@ struct BrFwdK {
   int ldres, lda, C8;
 };
 
-// the statistics prologue of bn_act_fwd_body, for one operand: scale / shift of every channel into LDS
-__device__ __forceinline__ void br_prologue(const BrNormFwd& n, const int C, const int bid, float* s_sc, float* s_sh) {
-  const int CA = BR_ACC_C(C);
-  if (n.acc) {
-    for (int c = threadIdx.x; c < C; c += 256) {
-      f64x2 v[MI_BN_SLOTS];
-#pragma unroll
-      for (int k = 0; k < MI_BN_SLOTS; ++k)
-        v[k] = k < n.nslots ? *(const f64x2*)(n.acc + ((size_t)k * CA + c) * 2) : f64x2{0.0, 0.0};
-      double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-      for (int k = 0; k < MI_BN_SLOTS; ++k) {
-        s1 += v[k][0];
-        s2 += v[k][1];
-      }
-      const double mean = s1 * n.inv_count;
-      double var = s2 * n.inv_count - mean * mean;
-      if (var < 0.0) var = 0.0;
-      const double invstd = 1.0 / sqrt(var + (double)n.eps);
-      const float g = n.gamma[c], b = n.beta[c];
-      const float sc = (float)((double)g * invstd);
-      const float sh = (float)((double)b - mean * (double)g * invstd);
-      s_sc[c] = sc;
-      s_sh[c] = sh;
-      if (bid == 0) {
-        n.scale[c] = sc;
-        n.shift[c] = sh;
-        n.mean[c] = (float)mean;
-        n.invstd[c] = (float)invstd;
-        if (n.rmean) n.rmean[c] = (1.f - n.momentum) * n.rmean[c] + n.momentum * (float)mean;
-        if (n.rvar) n.rvar[c] = (1.f - n.momentum) * n.rvar[c] + n.momentum * (float)(var * n.unbias);
-        if (c == 0 && n.nbt) *n.nbt += 1;
-      }
-    }
-  } else {
-    for (int c = threadIdx.x; c < C; c += 256) {
-      s_sc[c] = n.scale[c];
-      s_sh[c] = n.shift[c];
-    }
-  }
-}
-
 template <int FORM, int RELU>
 __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(const BrFwdK p) {
-  __shared__ float s_sc[FORM == 1 ? 2 : 1][BR_MAXC], s_sh[FORM == 1 ? 2 : 1][BR_MAXC];
+  __shared__ float s_sc[FORM == 1 ? 2 : 1][BN_MAXC], s_sh[FORM == 1 ? 2 : 1][BN_MAXC];
   const int bid = blockIdx.x, nb = gridDim.x;
   const int C8 = p.C8, C = C8 * 8;
-  br_prologue(p.n[0], C, bid, s_sc[0], s_sh[0]);
-  if (FORM == 1) br_prologue(p.n[1], C, bid, s_sc[FORM == 1 ? 1 : 0], s_sh[FORM == 1 ? 1 : 0]);
+  bn_fwd_prologue<false>(p.n[0], C, bid, s_sc[0], s_sh[0]);
+  if (FORM == 1) bn_fwd_prologue<false>(p.n[1], C, bid, s_sc[FORM == 1 ? 1 : 0], s_sh[FORM == 1 ? 1 : 0]);
   __syncthreads();
   const int64_t total = p.npix * C8;
   const int TPB = (256 / C8) * C8;
@@ -150,35 +106,7 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(const BrFwdK p) {
   }
 }
 
-// ------------------------------------------------------------------ channel sums: the shared tail of stats and reduce
-// red[pl][c8][8 * NS] -> one fp32 sum per (channel, quantity) and block, added to the block's slot with an fp64 atomic:
-// quantity 0 -> d1[c][0] (and d2[c][0] when there is a second operand: sum dz is common to both), 1 -> d1[c][1], 2 -> d2[c][1]
-template <int NS>
-__device__ __forceinline__ void br_block_sums(float* red, const float (*s)[8], const int C8, const int PL, const bool active,
-                                              const int pl, const int c8, double* d1, double* d2) {
-  const int tid = threadIdx.x;
-  if (active) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[(pl * C8 + c8) * (8 * NS) + q * 8 + e] = s[q][e];
-  }
-  __syncthreads();
-  const int nout = C8 * 8 * NS;
-  for (int j = tid; j < nout; j += 256) {
-    float acc = 0.f;
-    for (int q = 0; q < PL; ++q) acc += red[q * nout + j];
-    const int cc8 = j / (8 * NS), v = j % (8 * NS);
-    const int c = cc8 * 8 + (v & 7), q = v >> 3;
-    if (q == 2) {
-      atomicAdd(d2 + c * 2 + 1, (double)acc);
-    } else {
-      atomicAdd(d1 + c * 2 + q, (double)acc);
-      if (NS == 3 && q == 0) atomicAdd(d2 + c * 2, (double)acc);
-    }
-  }
-}
-
+// ------------------------------------------------------------------ statistics of a map without a statistics epilogue
 struct BrStatsK {
   const __bf16* x;
   double* acc;
@@ -213,8 +141,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const BrStatsK p) {
       }
     }
   }
-  double* slot = p.acc + (size_t)(bid % p.nslots) * BR_ACC_C(C8 * 8) * 2;
-  br_block_sums<2>(red, s, C8, PL, active, pl, c8, slot, nullptr);
+  double* slot = p.acc + (size_t)(bid % p.nslots) * BN_ACC_C(C8 * 8) * 2;
+  bn_block_sums<2>(red, s, C8, PL, active, pl, c8, slot, nullptr);
 }
 
 // ------------------------------------------------------------------ backward
@@ -288,43 +216,21 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const BrBwdK p)
       if (STORE) *(bf16x8*)(p.dres + (pix0 + u * pstride) * p.lddres + c8 * 8) = pack8(dzv);   // (exact: da or 0)
     }
   }
-  const size_t so = (size_t)BR_ACC_C(C8 * 8) * 2;
+  const size_t so = (size_t)BN_ACC_C(C8 * 8) * 2;
   double* d1 = p.n[0].dacc + (size_t)(bid % p.n[0].nslots) * so;
   double* d2 = TWO ? p.n[1].dacc + (size_t)(bid % p.n[1].nslots) * so : nullptr;
-  br_block_sums<NS>(red, s, C8, PL, active, pl, c8, d1, d2);
+  bn_block_sums<NS>(red, s, C8, PL, active, pl, c8, d1, d2);
 }
 
 // pass 2
-__device__ __forceinline__ void br_bwd_prologue(const BrNormBwd& n, const int C, const int bid, float* s_c1, float* s_c2) {
-  const int CA = BR_ACC_C(C);
-  for (int c = threadIdx.x; c < C; c += 256) {
-    f64x2 v[MI_BN_SLOTS];
-#pragma unroll
-    for (int k = 0; k < MI_BN_SLOTS; ++k)
-      v[k] = k < n.nslots ? *(const f64x2*)(n.dacc + ((size_t)k * CA + c) * 2) : f64x2{0.0, 0.0};
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < MI_BN_SLOTS; ++k) {
-      s1 += v[k][0];
-      s2 += v[k][1];
-    }
-    s_c1[c] = (float)(s1 * n.inv_count);
-    s_c2[c] = (float)(s2 * n.inv_count);
-    if (bid == 0) {
-      if (n.dbeta) n.dbeta[c] = (float)s1;
-      if (n.dgamma) n.dgamma[c] = (float)s2;
-    }
-  }
-}
-
 // FROMDZ: reduce stored dz in dres (see there); da, a are not read and dres is not written again
 template <int TWO, int RELU, int FROMDZ>
 __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const BrBwdK p) {
-  __shared__ float s_c1[TWO ? 2 : 1][BR_MAXC], s_c2[TWO ? 2 : 1][BR_MAXC];
+  __shared__ float s_c1[TWO ? 2 : 1][BN_MAXC], s_c2[TWO ? 2 : 1][BN_MAXC];
   const int bid = blockIdx.x, nb = gridDim.x;
   const int C8 = p.C8, C = C8 * 8;
-  br_bwd_prologue(p.n[0], C, bid, s_c1[0], s_c2[0]);
-  if (TWO) br_bwd_prologue(p.n[1], C, bid, s_c1[TWO ? 1 : 0], s_c2[TWO ? 1 : 0]);
+  bn_bwd_prologue(p.n[0], C, bid, s_c1[0], s_c2[0]);
+  if (TWO) bn_bwd_prologue(p.n[1], C, bid, s_c1[TWO ? 1 : 0], s_c2[TWO ? 1 : 0]);
   __syncthreads();
   const int64_t total = p.npix * C8;
   const int TPB = (256 / C8) * C8;
@@ -401,31 +307,30 @@ static int br_blocks(int64_t total, int64_t per) {
   if (b < 1) b = 1;
   return (int)b;
 }
-static inline int br_slots(int nslots) { return (nslots >= 1 && nslots <= MI_BN_SLOTS) ? nslots : MI_BN_SLOTS; }
 
 static int br_check_common(const mi_bn_relu_desc* d, const char* who) {
   MI_REQUIRE(d != nullptr, "%s: null descriptor", who);
-  MI_REQUIRE(d->C > 0 && d->C % 8 == 0 && d->C <= BR_MAXC, "%s: C %d (need C %% 8 == 0, 0 < C <= %d)", who, d->C, BR_MAXC);
+  MI_REQUIRE(d->C > 0 && d->C % 8 == 0 && d->C <= BN_MAXC, "%s: C %d (need C %% 8 == 0, 0 < C <= %d)", who, d->C, BN_MAXC);
   MI_REQUIRE(d->npix > 0, "%s: npix %lld is not positive", who, (long long)d->npix);
   MI_REQUIRE(d->n1.y != nullptr, "%s: null n1.y (the main operand is mandatory)", who);
   return MI_OK;
 }
 static int br_check_view(const void* p, int ld, int C, const char* who, const char* name) {
   MI_REQUIRE(ld % 8 == 0 && ld >= C, "%s: leading dimension %s %d is not a multiple of 8 that is >= C %d", who, name, ld, C);
-  MI_REQUIRE(br_al16(p), "%s: %s is not 16-byte aligned", who, name);
+  MI_REQUIRE(bn_al16(p), "%s: %s is not 16-byte aligned", who, name);
   return MI_OK;
 }
 
 extern "C" int mi_bn_relu_desc_size(void) { return (int)sizeof(mi_bn_relu_desc); }
 
 extern "C" int mi_bn_stats(const void* x, int ldx, int64_t npix, int C, double* acc, int nslots, mi_stream_t st) {
-  MI_REQUIRE(C > 0 && C % 8 == 0 && C <= BR_MAXC, "mi_bn_stats: C %d (need C %% 8 == 0, 0 < C <= %d)", C, BR_MAXC);
+  MI_REQUIRE(C > 0 && C % 8 == 0 && C <= BN_MAXC, "mi_bn_stats: C %d (need C %% 8 == 0, 0 < C <= %d)", C, BN_MAXC);
   MI_REQUIRE(npix > 0, "mi_bn_stats: npix %lld is not positive", (long long)npix);
   MI_REQUIRE(x != nullptr && acc != nullptr, "mi_bn_stats: null x / acc");
   if (int rc = br_check_view(x, ldx, C, "mi_bn_stats", "ldx / x")) return rc;
-  MI_REQUIRE(br_al16(acc), "mi_bn_stats: acc is not 16-byte aligned");
+  MI_REQUIRE(bn_al16(acc), "mi_bn_stats: acc is not 16-byte aligned");
   BrStatsK k;
-  k.x = (const __bf16*)x; k.acc = acc; k.npix = npix; k.ldx = ldx; k.C8 = C / 8; k.nslots = br_slots(nslots);
+  k.x = (const __bf16*)x; k.acc = acc; k.npix = npix; k.ldx = ldx; k.C8 = C / 8; k.nslots = bn_slots(nslots);
   hipLaunchKernelGGL(bn_stats_kernel, dim3(br_blocks(npix * (C / 8), 2048)), dim3(256), 0, (hipStream_t)st, k);
   MI_CHECK_LAUNCH("bn_stats");
   return MI_OK;
@@ -436,12 +341,12 @@ static int br_fill_fwd(const mi_bn_relu_norm& n, int C, const char* who, const c
   MI_REQUIRE(n.scale != nullptr && n.shift != nullptr, "%s: null scale / shift of %s", who, name);
   MI_REQUIRE(!n.acc || (n.gamma && n.beta && n.mean && n.invstd && n.count > 0),
              "%s: train mode needs gamma / beta / mean / invstd and a positive count of %s", who, name);
-  MI_REQUIRE(br_al16(n.acc), "%s: acc of %s is not 16-byte aligned", who, name);
+  MI_REQUIRE(bn_al16(n.acc), "%s: acc of %s is not 16-byte aligned", who, name);
   o->y = (const __bf16*)n.y; o->acc = n.acc; o->gamma = n.gamma; o->beta = n.beta; o->rmean = n.running_mean;
   o->rvar = n.running_var; o->nbt = n.num_batches_tracked; o->scale = n.scale; o->shift = n.shift; o->mean = n.mean;
   o->invstd = n.invstd; o->inv_count = n.count > 0 ? 1.0 / (double)n.count : 0.0;
   o->unbias = n.count > 1 ? (double)n.count / (double)(n.count - 1) : 1.0;
-  o->eps = n.eps; o->momentum = n.momentum; o->ldy = n.ldy; o->nslots = br_slots(n.nslots);
+  o->eps = n.eps; o->momentum = n.momentum; o->ldy = n.ldy; o->nslots = bn_slots(n.nslots);
   return MI_OK;
 }
 
@@ -478,14 +383,14 @@ extern "C" int mi_bn_relu_fwd(const mi_bn_relu_desc* d, mi_stream_t st) {
 static int br_fill_bwd(const mi_bn_relu_norm& n, int C, bool apply, const char* who, const char* name, BrNormBwd* o) {
   if (int rc = br_check_view(n.y, n.ldy, C, who, name)) return rc;
   MI_REQUIRE(n.mean != nullptr && n.invstd != nullptr && n.dacc != nullptr, "%s: null mean / invstd / dacc of %s", who, name);
-  MI_REQUIRE(br_al16(n.dacc), "%s: dacc of %s is not 16-byte aligned", who, name);
+  MI_REQUIRE(bn_al16(n.dacc), "%s: dacc of %s is not 16-byte aligned", who, name);
   if (apply) {
     MI_REQUIRE(n.gamma != nullptr && n.dy != nullptr && n.count > 0, "%s: null gamma / dy or no count of %s", who, name);
     if (int rc = br_check_view(n.dy, n.lddy, C, who, "dy")) return rc;
   }
   o->y = (const __bf16*)n.y; o->mean = n.mean; o->invstd = n.invstd; o->gamma = n.gamma; o->dacc = n.dacc;
   o->dy = (__bf16*)n.dy; o->dgamma = n.dgamma; o->dbeta = n.dbeta; o->inv_count = n.count > 0 ? 1.0 / (double)n.count : 0.0;
-  o->ldy = n.ldy; o->lddy = n.lddy; o->nslots = br_slots(n.nslots); o->pad_ = 0;
+  o->ldy = n.ldy; o->lddy = n.lddy; o->nslots = bn_slots(n.nslots); o->pad_ = 0;
   return MI_OK;
 }
 

@@ -4,6 +4,7 @@
 // launch.  Used by bn_act.hip (fused BatchNorm backward) and by the two convolution kernels.
 #pragma once
 #include "common.h"
+#include "bn_common.h"
 
 #define BN_FUS_SPIN_LIMIT (1 << 22)
 // Grid-wide barrier over nb resident blocks.  Agent-scope atomics are performed memory-side, one after the other per
@@ -20,35 +21,47 @@ __device__ __forceinline__ unsigned* bn_bar_cnt(unsigned* bar, int g) { return b
 // acknowledged when the block passes its __syncthreads (workgroup release = s_waitcnt vmcnt(0)), and read back after the
 // barrier by agent-scope atomic loads, which bypass the non-coherent caches.
 // *gave_up (LDS) = 1 when this block's wait timed out: its sums are incomplete and it must poison what it writes.
+// thread 0 of a block: the three steps the barrier forms below are composed of
+__device__ __forceinline__ int bn_bar_group(const int bid, const int nb) { return bid % (nb < BN_BAR_G ? nb : BN_BAR_G); }
+// count this block's arrival; true for the block that arrives last of all (it has reset the counters for the next launch)
+__device__ __forceinline__ bool bn_bar_count(unsigned* bar, const int bid, const int nb) {
+  const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
+  const int g = bid % G;
+  const unsigned gsize = (unsigned)((nb - g + G - 1) / G);
+  if (__hip_atomic_fetch_add(bn_bar_cnt(bar, g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
+    __hip_atomic_store(bn_bar_cnt(bar, g), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)G - 1u) {
+      __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return true;
+    }
+  }
+  return false;
+}
+// the last block: let every group go
+__device__ __forceinline__ void bn_bar_release(unsigned* bar, const int nb) {
+  const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
+  for (int q = 0; q < G; ++q) __hip_atomic_fetch_add(bn_bar_gen(bar, q), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// wait until the generation of this block's group has moved on from gen0; true when the wait gave up
+__device__ __forceinline__ bool bn_bar_wait(unsigned* bar, const unsigned gen0, const int bid, const int nb) {
+  int spins = 0;
+  while (__hip_atomic_load(bn_bar_gen(bar, bn_bar_group(bid, nb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen0) {
+    __builtin_amdgcn_s_sleep(8);
+    if (++spins > BN_FUS_SPIN_LIMIT) {  // a block that never became resident: report instead of hanging the GPU
+      __hip_atomic_store(bar + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return true;
+    }
+  }
+  return false;
+}
+
 __device__ __forceinline__ void bn_grid_barrier(unsigned* bar, const unsigned gen0, const int bid, const int nb, int* gave_up) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (see bn_bar_arrive)
   __syncthreads();
   if (threadIdx.x == 0) {
     *gave_up = 0;
-    const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
-    const int g = bid % G;
-    const unsigned gsize = (unsigned)((nb - g + G - 1) / G);
-    bool released = false;
-    if (__hip_atomic_fetch_add(bn_bar_cnt(bar, g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
-      __hip_atomic_store(bn_bar_cnt(bar, g), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)G - 1u) {
-        __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int q = 0; q < G; ++q)
-          __hip_atomic_fetch_add(bn_bar_gen(bar, q), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        released = true;
-      }
-    }
-    if (!released) {
-      int spins = 0;
-      while (__hip_atomic_load(bn_bar_gen(bar, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen0) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > BN_FUS_SPIN_LIMIT) {  // a block that never became resident: report instead of hanging the GPU
-          __hip_atomic_store(bar + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          *gave_up = 1;
-          break;
-        }
-      }
-    }
+    if (bn_bar_count(bar, bid, nb)) bn_bar_release(bar, nb);
+    else if (bn_bar_wait(bar, gen0, bid, nb)) *gave_up = 1;
   }
   __syncthreads();
 }
@@ -63,17 +76,7 @@ __device__ __forceinline__ void bn_bar_arrive(unsigned* bar, const int bid, cons
   __syncthreads();
   if (threadIdx.x == 0) {
     *gave_up = 0;
-    *is_last = 0;
-    const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
-    const int g = bid % G;
-    const unsigned gsize = (unsigned)((nb - g + G - 1) / G);
-    if (__hip_atomic_fetch_add(bn_bar_cnt(bar, g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
-      __hip_atomic_store(bn_bar_cnt(bar, g), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)G - 1u) {
-        __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *is_last = 1;
-      }
-    }
+    *is_last = bn_bar_count(bar, bid, nb) ? 1 : 0;
   }
   __syncthreads();
 }
@@ -82,22 +85,8 @@ __device__ __forceinline__ void bn_bar_finish(unsigned* bar, const unsigned gen0
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last block's agent-scope stores of the folded totals: acknowledged
   __syncthreads();
   if (threadIdx.x == 0) {
-    const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
-    const int g = bid % G;
-    if (*is_last) {
-      for (int q = 0; q < G; ++q)
-        __hip_atomic_fetch_add(bn_bar_gen(bar, q), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      int spins = 0;
-      while (__hip_atomic_load(bn_bar_gen(bar, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen0) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > BN_FUS_SPIN_LIMIT) {  // a block that never became resident: report instead of hanging the GPU
-          __hip_atomic_store(bar + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          *gave_up = 1;
-          break;
-        }
-      }
-    }
+    if (*is_last) bn_bar_release(bar, nb);
+    else if (bn_bar_wait(bar, gen0, bid, nb)) *gave_up = 1;
   }
   __syncthreads();
 }
@@ -121,8 +110,8 @@ struct CBnFwd {
   float eps, momentum;
 };
 
-// channel c's (scale, shift) from ITS fp64 accumulators acc[slot * sld + {0, 1}] (acc points at the channel) - the arithmetic of
-// bn_act_fwd_body (bn_act.hip), bit for bit.  Agent-scope loads: the sums were added memory-side by every block.
+// channel c's (scale, shift) from ITS fp64 accumulators acc[slot * sld + {0, 1}] (acc points at the channel): bn_moments /
+// bn_record of bn_common.h, as at every other site.  Agent-scope loads: the sums were added memory-side by every block.
 // `writer`: this lane also records scale / shift / mean / invstd and updates the running statistics (one lane per channel
 // of the launch); `poison` (NaN after a barrier timeout, else 0) marks results computed from incomplete sums.
 __device__ __forceinline__ void cbn_finalize(const CBnFwd& bn, const double* acc, int sld, int nslots, int c, bool writer,
@@ -143,26 +132,13 @@ __device__ __forceinline__ void cbn_finalize(const CBnFwd& bn, const double* acc
     s1 += v1[k];
     s2 += v2[k];
   }
-  const double mean = s1 * bn.inv_count;
-  double var = s2 * bn.inv_count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const double invstd = 1.0 / sqrt(var + (double)bn.eps);
-  const float g = bn.gamma[c], b = bn.beta[c];
-  const float sc = (float)((double)g * invstd) + poison;
-  const float sh = (float)((double)b - mean * (double)g * invstd) + poison;
+  float sc, sh;
+  const BnMoments m = bn_moments(s1, s2, bn.inv_count, bn.eps, bn.gamma[c], bn.beta[c], sc, sh);
+  sc += poison;
+  sh += poison;
   sc_out = sc;
   sh_out = sh;
-  if (writer) {
-    bn.scale[c] = sc;
-    bn.shift[c] = sh;
-    bn.mean[c] = (float)mean + poison;
-    bn.invstd[c] = (float)invstd + poison;
-    if (bn.rmean) {
-      bn.rmean[c] = (1.f - bn.momentum) * bn.rmean[c] + bn.momentum * (float)mean;
-      bn.rvar[c] = (1.f - bn.momentum) * bn.rvar[c] + bn.momentum * (float)(var * bn.unbias);
-    }
-    if (c == 0 && bn.nbt) *bn.nbt += 1;
-  }
+  if (writer) bn_record<true>(bn, c, sc, sh, m, poison);
 }
 
 // 8 channels of one pixel: a = act(y * scale + shift) (+ res), the expression of bn_act_fwd_body
@@ -197,8 +173,8 @@ struct BnXf {
 static_assert(sizeof(BnXf) == sizeof(mi_bnx) && __builtin_offsetof(BnXf, acc) == __builtin_offsetof(mi_bnx, acc) &&
               __builtin_offsetof(BnXf, bn.inv_count) == __builtin_offsetof(mi_bnx, inv_count) &&
               __builtin_offsetof(BnXf, bn.lda) == __builtin_offsetof(mi_bnx, lda), "mi_bnx (include/mi355_det.h) mirrors BnXf");
-// every block: (scale, shift) of all C input channels into LDS tables - the arithmetic of bn_act_fwd_body's prologue, bit for
-// bit, with ITS loads: plain 16-byte loads, thread c next to thread c + 1 (the sums were completed by the previous launch;
+// every block: (scale, shift) of all C input channels into LDS tables - the arithmetic of bn_fwd_prologue (bn_common.h) with
+// ITS loads: plain 16-byte loads, thread c next to thread c + 1 (the sums were completed by the previous launch;
 // cbn_finalize's agent-scope 8-byte atomic loads are for readers BEHIND a grid barrier and cost one L2 request each: with
 // every block of a launch asking for the same C x nslots x 16 bytes they took ~9 us of a 512-channel 20x20 launch).
 // `rec`: this block also records scale / shift / mean / invstd for the backward pass and updates the running statistics
@@ -217,26 +193,11 @@ __device__ __forceinline__ void bnx_tables(const BnXf* __restrict__ xf, float* s
       s1 += k < nslots ? v[k][0] : 0.0;
       s2 += k < nslots ? v[k][1] : 0.0;
     }
-    const double mean = s1 * bn.inv_count;
-    double var = s2 * bn.inv_count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double invstd = 1.0 / sqrt(var + (double)bn.eps);
-    const float g = bn.gamma[c], b = bn.beta[c];
-    const float sc = (float)((double)g * invstd);
-    const float sh = (float)((double)b - mean * (double)g * invstd);
+    float sc, sh;
+    const BnMoments m = bn_moments(s1, s2, bn.inv_count, bn.eps, bn.gamma[c], bn.beta[c], sc, sh);
     s_sc[c] = sc;
     s_sh[c] = sh;
-    if (rec) {
-      bn.scale[c] = sc;
-      bn.shift[c] = sh;
-      bn.mean[c] = (float)mean;
-      bn.invstd[c] = (float)invstd;
-      if (bn.rmean) {
-        bn.rmean[c] = (1.f - bn.momentum) * bn.rmean[c] + bn.momentum * (float)mean;
-        bn.rvar[c] = (1.f - bn.momentum) * bn.rvar[c] + bn.momentum * (float)(var * bn.unbias);
-      }
-      if (c == 0 && bn.nbt) *bn.nbt += 1;
-    }
+    if (rec) bn_record<true>(bn, c, sc, sh, m, BN_NO_POISON);
   }
 }
 // one 16-byte piece (8 channels cg * 8 .. of one pixel), in place; returns what it wrote
