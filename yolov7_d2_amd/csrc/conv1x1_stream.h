@@ -105,6 +105,10 @@ __global__ __launch_bounds__(WM* WN * 64) void c1s_kernel(const C1K p) {
   constexpr int X2 = NBUF > 3 ? (NBUF - 4) * D + 2 * (2 * D + S) : (NBUF - 1) * S + (NBUF - 2) * 2 * D;
   constexpr int X3 = (NBUF - 1) * S + (NBUF - 2) * 2 * D;
   static_assert(!XF || (X3 < 64 && X2 < 64 && X1 < 64), "vmcnt field");
+  // ... and newer than the block's LAST DMA when the tile loop has ended (statistics modes: L = 0, every store issued): the
+  // last tile's S stores; the writer's side stores of that iteration precede its DMA
+  constexpr int WT = S;
+  static_assert(WT < 64, "vmcnt field");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
@@ -377,41 +381,17 @@ __global__ __launch_bounds__(WM* WN * 64) void c1s_kernel(const C1K p) {
     nbuf = nbuf + 1 == NBUF ? 0 : nbuf + 1;
   }
 
-  C1_VMCNT(0);   // the tail DMAs still target this block's LDS
   if constexpr (STATS) {
-    // one set of atomics per block: lanes fold over their 32 pixels, waves over the WN pixel groups through LDS
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        s1[r] += __shfl_xor(s1[r], off, 64);
-        s2[r] += __shfl_xor(s2[r], off, 64);
-      }
-    __syncthreads();
-    float* red = (float*)smem;   // [WN][WM * 32][2]
-    if (l31 == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int c = wm * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
-        red[(wn * WM * 32 + c) * 2 + 0] = s1[r];
-        red[(wn * WM * 32 + c) * 2 + 1] = s2[r];
-      }
-    }
-    __syncthreads();
-    if (wave < WM && lane < 32) {
-      float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-      for (int q = 0; q < WN; ++q) {
-        a1 += red[(q * WM * 32 + wave * 32 + lane) * 2 + 0];
-        a2 += red[(q * WM * 32 + wave * 32 + lane) * 2 + 1];
-      }
-      const C1Slice so = p.s[cot * WM + wave];
-      double* sp = so.stats + (size_t)((int)blockIdx.x % so.nslots) * so.sld + lane * 2;
-      if (!(p.dbg & 1)) {
-        atomicAdd(sp, (double)a1);
-        atomicAdd(sp + 1, (double)a2);
-      }
-    }
+    // the tail DMAs still target this block's LDS, and are older than the last tile's stores: those stay in flight beside
+    // the block's statistics (conv_bn.h): lanes fold over their 32 pixels, waves over the WN pixel groups through LDS, one
+    // set of atomics per block
+    C1_VMCNT(WT);
+    cbn_block_stats<WM, WN>(s1, s2, (float*)smem, wave, lane, (p.dbg & 1) != 0, [&](const int c) {
+      const C1Slice& so = p.s[cot * WM + (c >> 5)];
+      return so.stats + (size_t)((int)blockIdx.x % so.nslots) * so.sld + (c & 31) * 2;
+    });
+  } else {
+    C1_VMCNT(0);   // the tail DMAs still target this block's LDS
   }
   if constexpr (MODE == 3) {
     // ---- phase 2: every block's sums are in; BatchNorm + activation of this block's own tiles

@@ -17,7 +17,8 @@
 //     tile kernel needs a VGPR address per (k-step, tap column, pixel group), 6.4 VALU per MFMA);
 //   * 9 x K/16 k-steps run back to back without any synchronisation (288 MFMAs per wave and tile at K = 128);
 //   * outputs: bf16 -> permlane32_swap -> 16 contiguous bytes per lane, stored during the NEXT tile's main loop; BatchNorm
-//     sums per lane, parked in LDS between tiles, one set of fp64 atomics per block.
+//     sums per lane (in registers, or parked in LDS between tiles where the weights leave no room), one set of fp64 atomics
+//     per block (conv_bn.h, cbn_block_stats).
 // A launch carries up to 8 jobs (the head's three levels x two towers run as one launch); a block belongs to one job.
 // MODE 0: plain, 1: + BatchNorm statistics, 2: y += result, 3: MODE 1 and then, behind a grid barrier, BatchNorm(train) +
 // SiLU (+ residual) of the block's own output tiles (conv_bn.h; see conv1x1_stream.h MODE 3): conv2 + bn + act + shortcut
@@ -206,13 +207,23 @@ __global__ __launch_bounds__(WM* WN * 64, (K == 128 || (S == 2 && K == 64)) ? 1 
     return ((py < H) & (px < Wd)) ? q : nullptr;
   };
 
-  // BatchNorm sums: per lane 16 channels x (sum, sumsq), kept in LDS between tiles ([8][threads][16 B] behind the two halo
-  // buffers) - 32 more live registers across the main loop do not fit next to the weights
+  // BatchNorm sums: per lane 16 channels x (sum, sumsq).  In registers for the whole launch where 32 more live registers
+  // across the main loop cost neither scratch nor an occupancy step: K = 32 stride 1 (72 VGPRs of weights, three waves per
+  // SIMD as before) and K = 64 stride 2 (one block per CU).  Elsewhere parked in LDS between tiles ([8][threads][16 B] behind
+  // the two halo buffers): K = 128 holds 288 VGPRs of weights, K = 64 stride 1 (two blocks per CU, 256 VGPRs) spills 160 bytes
+  // per lane with them, K = 32 stride 2 drops from three waves per SIMD to two.
+  constexpr bool SREG = (K == 32 && S == 1) || (K == 64 && S == 2);
   float* const sacc = (float*)(smem + 2 * XB) + tid * 4;
   constexpr int SAS = NW * 64 * 4;   // floats between the 8 vectors of a lane
+  float s1[16], s2[16];
   if constexpr (STATS) {
+    if constexpr (SREG) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) *(f32x4*)(sacc + q * SAS) = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int r = 0; r < 16; ++r) s1[r] = s2[r] = 0.f;
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) *(f32x4*)(sacc + q * SAS) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
   }
 
   Org oc = tile_origin(0), op = oc;   // current / previous tile
@@ -325,8 +336,7 @@ __global__ __launch_bounds__(WM* WN * 64, (K == 128 || (S == 2 && K == 64)) ? 1 
         asm volatile("s_waitcnt vmcnt(0)"
                      : "+v"(old[0]), "+v"(old[1]), "+v"(old[2]), "+v"(old[3]), "+v"(old[4]), "+v"(old[5]), "+v"(old[6]), "+v"(old[7])::"memory");
     }
-    float s1[16], s2[16];
-    if constexpr (STATS) {
+    if constexpr (STATS && !SREG) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const f32x4 u = *(const f32x4*)(sacc + q * SAS), w = *(const f32x4*)(sacc + (4 + q) * SAS);
@@ -373,7 +383,7 @@ __global__ __launch_bounds__(WM* WN * 64, (K == 128 || (S == 2 && K == 64)) ? 1 
         pk[g * 2 + pr] = v;
       }
     }
-    if constexpr (STATS) {
+    if constexpr (STATS && !SREG) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         *(f32x4*)(sacc + q * SAS) = f32x4{s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]};
@@ -390,46 +400,20 @@ __global__ __launch_bounds__(WM* WN * 64, (K == 128 || (S == 2 && K == 64)) ? 1 
     if (o) *(u32x4*)(o + (q % 2) * 32) = pk[q];
   }
 
-  W3_VMCNT(0);
+  // No wait for those stores: every LDS-DMA of the block was waited for at the top of the last iteration (the last tile
+  // issues none), so nothing targets the ring any more and the stores run beside the block's statistics (conv_bn.h)
   if constexpr (STATS) {
-    float s1[16], s2[16];
+    if constexpr (!SREG) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 u = *(const f32x4*)(sacc + q * SAS), w = *(const f32x4*)(sacc + (4 + q) * SAS);
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 u = *(const f32x4*)(sacc + q * SAS), w = *(const f32x4*)(sacc + (4 + q) * SAS);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { s1[4 * q + e] = u[e]; s2[4 * q + e] = w[e]; }
-    }
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        s1[r] += __shfl_xor(s1[r], off, 64);
-        s2[r] += __shfl_xor(s2[r], off, 64);
-      }
-    __syncthreads();
-    float* red = (float*)smem;   // [WN][WM * 32][2]
-    if (l31 == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int c = wm * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
-        red[(wn * WM * 32 + c) * 2 + 0] = s1[r];
-        red[(wn * WM * 32 + c) * 2 + 1] = s2[r];
+        for (int e = 0; e < 4; ++e) { s1[4 * q + e] = u[e]; s2[4 * q + e] = w[e]; }
       }
     }
-    __syncthreads();
-    if (tid < WM * 32) {
-      float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-      for (int q = 0; q < WN; ++q) {
-        a1 += red[(q * WM * 32 + tid) * 2 + 0];
-        a2 += red[(q * WM * 32 + tid) * 2 + 1];
-      }
-      double* sp = jb.stats + (size_t)((int)blockIdx.x % jb.nslots) * jb.sld + tid * 2;
-      if (!(p.dbg & 1)) {
-        atomicAdd(sp, (double)a1);
-        atomicAdd(sp + 1, (double)a2);
-      }
-    }
+    cbn_block_stats<WM, WN>(s1, s2, (float*)smem, wave, lane, (p.dbg & 1) != 0, [&](const int c) {
+      return jb.stats + (size_t)((int)blockIdx.x % jb.nslots) * jb.sld + c * 2;
+    });
   }
   if constexpr (MODE == 3) {
     // ---- phase 2: every block's sums are in; BatchNorm + activation (+ residual) of this block's own tiles

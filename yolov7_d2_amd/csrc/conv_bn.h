@@ -158,6 +158,88 @@ __device__ __forceinline__ u32x4 cbn_apply8(const u32x4 yv, const float* sc, con
   return __builtin_bit_cast(u32x4, pack8(o));
 }
 
+// ---- the block's BatchNorm (sum, sumsq) of a persistent convolution launch: the tail behind the tile loop of c1s_kernel /
+// w3_kernel (MODE 1, 3, XF).  Every lane arrives with 16 channels x (sum, sumsq) over ITS pixels: lane (l31, h) of wave
+// (wm, wn) holds channel wm * 32 + 8 (r >> 2) + 4 h + (r & 3) in register r (the MFMA accumulator order).
+// value of lane (lane ^ OFF), OFF < 32: DPP where gfx950 has a form with these operands (quad_perm for 1 and 2, a rotation
+// by half a row for 8), ds_bpermute for 4 and 16.  Called with every lane active.
+template <int OFF>
+__device__ __forceinline__ float cbn_lane_xor(const float v) {
+  const int i = __builtin_bit_cast(int, v);
+  if constexpr (OFF == 1) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, i, 0xB1, 0xF, 0xF, true));        // quad_perm:[1,0,3,2]
+  else if constexpr (OFF == 2) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, i, 0x4E, 0xF, 0xF, true));   // quad_perm:[2,3,0,1]
+  else if constexpr (OFF == 8) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, i, 0x128, 0xF, 0xF, true));  // row_ror:8
+  else return __shfl_xor(v, OFF, 64);
+}
+// One level of the halving exchange over the lane pairs (l, l ^ OFF): the lane whose OFF bit is clear keeps registers
+// [0, N), the other one [N, 2 N); each receives the partner's values of the half it keeps.  out[k] = own + partner's: the
+// sum the full butterfly `s[r] += shfl_xor(s[r], OFF)` leaves in BOTH lanes (an fp32 addition commutes bit for bit), so the
+// pairing tree of every channel - and with it every bit of the block's partial sums - is the butterfly's.
+template <int N, int OFF>
+__device__ __forceinline__ void cbn_halve(const float (&in)[2 * N], float (&out)[N], const bool up) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const float keep = up ? in[k + N] : in[k], send = up ? in[k] : in[k + N];
+    out[k] = keep + cbn_lane_xor<OFF>(send);
+  }
+}
+// 16 registers over the 32 lanes of a half-wave -> one: 8 + 4 + 2 + 1 exchanges, then one full exchange across xor 16 (16 in
+// place of the butterfly's 80).  Lane l31 ends with register r = 8 b0 + 4 b1 + 2 b2 + b3 (b_i: bit i of l31); lanes l31 and
+// l31 ^ 16 hold the same value.
+__device__ __forceinline__ float cbn_fold32(const float (&s)[16], const int l31) {
+  float t8[8], t4[4], t2[2], t1[1];
+  cbn_halve<8, 1>(s, t8, (l31 & 1) != 0);
+  cbn_halve<4, 2>(t8, t4, (l31 & 2) != 0);
+  cbn_halve<2, 4>(t4, t2, (l31 & 4) != 0);
+  cbn_halve<1, 8>(t2, t1, (l31 & 8) != 0);
+  return t1[0] + cbn_lane_xor<16>(t1[0]);
+}
+// The tail.  `red`: the block's LDS from offset 0 (the tile ring: dead once every wave has passed the first barrier - the
+// caller has waited for ITS LDS-DMAs with a counted vmcnt, the output stores behind them stay in flight beside all of this);
+// stats_of(c): the (sum, sumsq) fp64 pair of the block's channel c = wm * 32 + .. in this block's slot.  WN > 1: the 16
+// owning lanes of each half-wave park their channel's pair in red[wn][c], one lane per channel adds the WN values in the
+// order 0 .. WN - 1 (from 0.f, as ever) and issues the two atomics.  WN == 1: no LDS stage and no barrier, the owning lanes
+// issue them.  noatom: the timing switch (MI_DEBUG_NOATOM), everything but the atomics.
+template <int WM, int WN, class StatsOf>
+__device__ __forceinline__ void cbn_block_stats(const float (&s1)[16], const float (&s2)[16], float* red, const int wave,
+                                                const int lane, const bool noatom, StatsOf&& stats_of) {
+#ifdef MI_CONV_STATS_NOTAIL   // diagnostic build (tools/build_variant.sh): the per-tile accumulation without the tail
+#pragma unroll
+  for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(s1[r]), "v"(s2[r]));
+  return;
+#endif
+  const int wm = wave / WN, wn = wave % WN, l31 = lane & 31, h = lane >> 5;
+  const float f1 = cbn_fold32(s1, l31), f2 = cbn_fold32(s2, l31);
+  const int r = ((l31 & 1) << 3) | ((l31 & 2) << 1) | ((l31 & 4) >> 1) | ((l31 & 8) >> 3);
+  const int c = wm * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
+  if constexpr (WN == 1) {
+    if (l31 < 16 && !noatom) {
+      double* sp = stats_of(c);
+      atomicAdd(sp, (double)f1);
+      atomicAdd(sp + 1, (double)f2);
+    }
+  } else {
+    // (the address - a slot division, the slice's table entry - before the barriers, not behind them)
+    double* const sp = stats_of((wave < WM ? wave : 0) * 32 + l31);
+    __syncthreads();   // every wave is done with the ring (its reads and its LDS-DMAs)
+    if (l31 < 16) *(float2*)(red + (wn * WM * 32 + c) * 2) = float2{f1, f2};   // red: [WN][WM * 32][2]
+    __syncthreads();
+    if (wave < WM && lane < 32) {
+      float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+      for (int q = 0; q < WN; ++q) {
+        const float2 v = *(const float2*)(red + (q * WM * 32 + wave * 32 + lane) * 2);
+        a1 += v.x;
+        a2 += v.y;
+      }
+      if (!noatom) {
+        atomicAdd(sp, (double)a1);
+        atomicAdd(sp + 1, (double)a2);
+      }
+    }
+  }
+}
+
 // ---- BatchNorm(train) + activation of a convolution's INPUT, applied by the consuming launch ("BN in the consumer")
 // The producer left the raw output y and its fp64 (sum, sumsq) accumulators; instead of a bn_act_fwd launch that reads y
 // and writes a = act(y * scale + shift), the consumer fetches y tiles (LDS-DMA), every wave rewrites the 16-byte pieces it
