@@ -314,6 +314,57 @@ int mi_gconv_dgrad(const mi_gconv_desc* d, mi_stream_t s);
 int64_t mi_gconv_wgrad_plan(const mi_gconv_desc* d, int32_t* nsplit);
 int mi_gconv_wgrad(const mi_gconv_desc* d, mi_stream_t s);
 
+/* ---- row-column decoupled attention (csrc/rcda.hip) ----------------------------------
+ * The attention core of Anchor DETR's MultiheadRCDA (backbone/layers/row_column_decoupled_attention.py), head_dim 32:
+ *   A_row[b,n,q,:] = softmax over w of scale * q_row[b,q,n,:] . k_row[b,w,n,:]   (-inf where mask_row[b][w])
+ *   A_col[b,n,q,:] = softmax over h of scale * q_col[b,q,n,:] . k_col[b,h,n,:]   (-inf where mask_col[b][h])
+ *   o[b,q,n,:]     = sum over h, w of A_col[b,n,q,h] * A_row[b,n,q,w] * v[b,h,w,n,:]
+ * bf16 operands, fp32 accumulation and softmax statistics; the weight A_col * A_row is rounded to bf16 once.  All tensors are
+ * batch first: q_row, q_col, dq_* [B][L] rows (row stride ldq), k_row, dk_row [B][W] rows and k_col, dk_col [B][H] rows (ldk:
+ * the projected means over H / W of the key maps), v, dv [B][H][W] rows (ldv), o, dout [B][L] rows (ldo); a row holds
+ * E = heads * 32 channels, head n in [32 n, 32 n + 32).  Strides are >= E and multiples of 8, base pointers 16-byte aligned.
+ * mask_row uint8 [B][W], mask_col uint8 [B][H] (1 = padded; either may be NULL).  lse_row, lse_col: fp32 [B][heads][L],
+ * written by the forward and read by the backward, in base-2 units (log2 of the sum of exp2(score * scale * log2 e)); -inf for
+ * a query whose row or column keys are all padded: its output is 0 and it contributes no gradient.
+ * Served: H, W <= 96, any L >= 1.  Anything else returns MI_EINVAL naming the quantity, before any launch.
+ * The backward writes every element of dq_row, dq_col, dk_row, dk_col, dv; its sums over queries run in a fixed order (no
+ * atomics: bit-reproducible).  ws: mi_rcda_bwd_ws_bytes() bytes of scratch (the two softmax gradients, bf16, for the key-side
+ * reduction).  No entry allocates, reads back or synchronises: every call can be captured into a graph.
+ * mi_rcda_key_mean: mean_row[b][w][:] = mean over h of key_row[b][h][w][:], mean_col[b][h][:] = mean over w of
+ * key_col[b][h][w][:] (bf16 [B][H][W][E] contiguous in, fp32 sums in index order, one rounding), both in one launch; either
+ * pair may be NULL. */
+typedef struct mi_rcda_desc {
+  const void* q_row;
+  const void* q_col;
+  const void* k_row;
+  const void* k_col;
+  const void* v;
+  const uint8_t* mask_row;
+  const uint8_t* mask_col;
+  void* o;              /* forward: written                                           */
+  float* lse_row;       /* forward: written; backward: read                           */
+  float* lse_col;
+  const void* dout;     /* backward only from here                                    */
+  void* dq_row;
+  void* dq_col;
+  void* dk_row;
+  void* dk_col;
+  void* dv;
+  void* ws;
+  int64_t ws_bytes;     /* >= mi_rcda_bwd_ws_bytes()                                  */
+  int32_t B, heads, L, H, W, E;
+  int32_t ldq, ldk, ldv, ldo;
+  float scale;          /* head_dim^-0.5 in the module                                */
+  int32_t rsv_;
+} mi_rcda_desc;
+int mi_rcda_desc_size(void);   /* sizeof(mi_rcda_desc) as compiled (binding self-check) */
+int mi_rcda_key_mean(const void* key_row, const void* key_col, void* mean_row, void* mean_col, int B, int H, int W, int E,
+                     mi_stream_t s);
+int mi_rcda_fwd(const mi_rcda_desc* d, mi_stream_t s);
+/* workspace bytes of mi_rcda_bwd for this geometry (pointers may be NULL), or < 0 */
+int64_t mi_rcda_bwd_ws_bytes(const mi_rcda_desc* d);
+int mi_rcda_bwd(const mi_rcda_desc* d, mi_stream_t s);
+
 /* ---- depthwise 3x3 convolution ------------------------------------------------
  * the `dconv` of DWConv (backbone/layers/wrappers.py:86-102: BaseConv(C, C, ksize, stride, groups=C); the reference
  * builds it with ksize 3 everywhere, darknetx.py:113-160): NHWC bf16, pad 1, stride 1 or 2, C % 8 == 0.

@@ -116,6 +116,14 @@ class mi_gconv_desc(C.Structure):
                                          "dilation", "rsv_")]
 
 
+class mi_rcda_desc(C.Structure):
+    """row-column decoupled attention (csrc/rcda.hip): one record for the forward and the backward"""
+    _fields_ = [(n, C.c_void_p) for n in ("q_row", "q_col", "k_row", "k_col", "v", "mask_row", "mask_col", "o", "lse_row", "lse_col",
+                                          "dout", "dq_row", "dq_col", "dk_row", "dk_col", "dv", "ws")] + [("ws_bytes", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("B", "heads", "L", "H", "W", "E", "ldq", "ldk", "ldv", "ldo")] + \
+               [("scale", C.c_float), ("rsv_", C.c_int32)]
+
+
 class mi_bn_relu_norm(C.Structure):
     """one norm operand of mi_bn_relu_desc (csrc/bn_relu.hip)"""
     _fields_ = [(n, C.c_void_p) for n in ("y", "acc", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked",
@@ -299,6 +307,11 @@ _PROTOS = {
     "mi_gconv_dgrad": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
     "mi_gconv_wgrad_plan": (C.c_int64, [C.POINTER(mi_gconv_desc), C.POINTER(C.c_int32)]),
     "mi_gconv_wgrad": (C.c_int, [C.POINTER(mi_gconv_desc), _vp]),
+    "mi_rcda_desc_size": (C.c_int, []),
+    "mi_rcda_key_mean": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mi_rcda_fwd": (C.c_int, [C.POINTER(mi_rcda_desc), _vp]),
+    "mi_rcda_bwd_ws_bytes": (C.c_int64, [C.POINTER(mi_rcda_desc)]),
+    "mi_rcda_bwd": (C.c_int, [C.POINTER(mi_rcda_desc), _vp]),
     "mi_bn_relu_desc_size": (C.c_int, []),
     "mi_bn_stats": (C.c_int, [_vp, _i, _i64, _i, _vp, _i, _vp]),
     "mi_bn_relu_fwd": (C.c_int, [C.POINTER(mi_bn_relu_desc), _vp]),

@@ -9,6 +9,7 @@ from .attention import mha_core
 from .iou_loss import IOUlossV6, IOUloss, pairwise_bbox_iou, bboxes_iou
 from .transformer import (MultiheadAttention, TransformerEncoderLayer, TransformerDecoderLayer, TransformerEncoder,
                           TransformerDecoder, Transformer)
+from .rcda import MultiheadRCDA, rcda_core
 from .position_encoding import PositionEmbeddingSine
 from .detr import DETR, MLP
 from .resnet import ResNet, build_resnet_backbone, FrozenBatchNorm2d, DeformConv, DeformBottleneckBlock
