@@ -113,8 +113,6 @@ class Interp:
     @staticmethod
     def members(c):
         """the symbolic builder commands behind a (possibly merged, possibly nested) materialised command, in order"""
-        if getattr(c, "fused_bn", False):
-            raise NotImplementedError(f"{c.tag}: conv + BatchNorm in one launch (MI_CONV_BN_FUSE=1) is not interpreted")
         ms = getattr(c, "members", None) or getattr(c, "parts", None)
         return [x for m in ms for x in Interp.members(m)] if ms else [c]
 

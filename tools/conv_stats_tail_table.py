@@ -33,7 +33,7 @@ for i, (c, ds) in enumerate(base):
         continue
     k = short(ds[0][0])
     m, _ = mode_of(k)
-    if (k.startswith(("c1s", "w3")) and m not in (1, 3)) or (c[1] == "CONV_GROUP" and not k.startswith(("c1s", "w3"))):
+    if (k.startswith(("c1s", "w3")) and m != 1) or (c[1] == "CONV_GROUP" and not k.startswith(("c1s", "w3"))):
         continue      # (a grouped launch on the tile kernel: the head's prediction convolutions, no BatchNorm behind them)
     us = [rows[t][0][i][1][0][1] for t in tags]
     shape = re.sub(r"tile\S+.*$", "", c[3]).strip()

@@ -469,7 +469,7 @@ struct BnFusK {
   __bf16* dy;
   __bf16* dres;
   double* dacc;
-  unsigned* bar;  // MI_BN_BAR_WORDS barrier words (bn_grid_barrier); [2] is set when a wait gave up (never in a healthy run)
+  unsigned* bar;  // MI_BN_BAR_WORDS barrier words (bn_bar_arrive / bn_bar_finish); [2] is set when a wait gave up (never in a healthy run)
   const float* scale;
   const float* shift;
   const float* mean;

@@ -19,7 +19,7 @@ struct BnMoments {
   double mean, var, invstd;
 };
 // folded sums (s1, s2) of one channel -> its moments and (scale, shift).  HOW the slots are loaded and folded stays with
-// the caller: that part is measured and differs on purpose (bn_slot_sums below, bnx_tables, cbn_finalize in conv_bn.h)
+// the caller: that part is measured and differs on purpose (bn_slot_sums below, bnx_tables in conv_bn.h)
 __device__ __forceinline__ BnMoments bn_moments(const double s1, const double s2, const double inv_count, const float eps,
                                                 const float g, const float b, float& sc, float& sh) {
   BnMoments m;

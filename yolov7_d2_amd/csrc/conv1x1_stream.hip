@@ -10,11 +10,9 @@ int c1s_launch_mode0(const C1Launch& l, hipStream_t s);
 int c1s_launch_mode1(const C1Launch& l, hipStream_t s);
 int c1s_launch_mode1x(const C1Launch& l, hipStream_t s);
 int c1s_launch_mode2(const C1Launch& l, hipStream_t s);
-int c1s_launch_mode3(const C1Launch& l, hipStream_t s);
 int c1s_launch_mode4(const C1Launch& l, hipStream_t s);
 int c1s_launch_mode5(const C1Launch& l, hipStream_t s);
 int c1s_launch_mode6(const C1Launch& l, hipStream_t s);
-int c1s_bar_status(unsigned* flag);
 
 static int c1s_cus() {
   static int cus = 0;
@@ -55,35 +53,12 @@ static bool c1s_desc_ok(const mi_conv_desc* d) {
   return true;
 }
 
-// the BatchNorm pass that follows convolution d, as the kernel's phase 2; false when the job does not describe exactly that
-bool cbn_from_job(const mi_conv_desc& d, const mi_bn_job& j, CBnFwd* o) {
-  const long long npix = (long long)d.N * d.outH * d.outW;
-  if (j.y != d.y || j.ldy != d.ldy || j.C != d.Cout || j.acc != d.stats_acc || !j.acc || !j.a) return false;
-  if (j.npix != npix || j.count != npix) return false;
-  const int nsl = (d.stats_slots >= 1 && d.stats_slots <= MI_BN_SLOTS) ? d.stats_slots : MI_BN_SLOTS;
-  if (j.nslots != nsl) return false;
-  if (!j.gamma || !j.beta || !j.scale || !j.shift || !j.mean || !j.invstd) return false;
-  if (j.lda % 8 || ((uintptr_t)j.a & 15) || npix * j.lda * 2 >= (1LL << 31)) return false;
-  if (j.res && (j.ldres % 8 || ((uintptr_t)j.res & 15) || npix * j.ldres * 2 >= (1LL << 31))) return false;
-  memset(o, 0, sizeof(*o));
-  o->res = (const __bf16*)j.res; o->a = (__bf16*)j.a;
-  o->gamma = j.gamma; o->beta = j.beta; o->rmean = j.rmean; o->rvar = j.rvar; o->nbt = (long long*)j.nbt;
-  o->scale = j.scale; o->shift = j.shift; o->mean = j.mean; o->invstd = j.invstd;
-  o->ldres = j.ldres; o->lda = j.lda; o->act = j.act;
-  o->inv_count = 1.0 / (double)j.count;                                    // (as mi_bn_act_fwd derives them)
-  o->unbias = j.count > 1 ? (double)j.count / (double)(j.count - 1) : 1.0;
-  o->eps = j.eps; o->momentum = j.momentum;
-  return true;
-}
-
 // n descriptors that read the same tensor -> one launch; returns false when the stream kernel does not apply.
-// bn (may be NULL): the BatchNorm jobs of the n convolutions -> MODE 3
 // c0 / cn (single descriptor only, cn > 0): the launch computes output channels [c0, c0 + cn) of the convolution - a layer
 // with more than 512 output channels runs as several launches over the same input (c1s_try_launch)
-static bool c1s_fill(const mi_conv_desc* ds, int n, C1Launch* l, const mi_bn_job* bn = nullptr, int c0 = 0, int cn = 0) {
+static bool c1s_fill(const mi_conv_desc* ds, int n, C1Launch* l, int c0 = 0, int cn = 0) {
   if (n < 1) return false;
-  if (bn && n > C1_MAX_BN) return false;
-  if (cn > 0 && (n != 1 || bn || cn % 32 || c0 % 32 || c0 + cn > ds[0].Cout)) return false;
+  if (cn > 0 && (n != 1 || cn % 32 || c0 % 32 || c0 + cn > ds[0].Cout)) return false;
   const mi_conv_desc& d0 = ds[0];
   int ns = 0;
   for (int j = 0; j < n; ++j) {
@@ -123,16 +98,12 @@ static bool c1s_fill(const mi_conv_desc* ds, int n, C1Launch* l, const mi_bn_job
   if (npix % tpix) {
     static const long minpix = getenv("MI_C1S_RAGGED_MINPIX") ? atol(getenv("MI_C1S_RAGGED_MINPIX")) : 8192;
     const bool mode_ok = l->MODE == 0 || l->MODE == 2 || l->MODE >= 4;
-    if (!mode_ok || bn || d0.xf || minpix < 0 || npix < minpix || npix < tpix) return false;
+    if (!mode_ok || d0.xf || minpix < 0 || npix < minpix || npix < tpix) return false;
     ragged = true;
-  }
-  if (bn) {
-    if (l->MODE != 1) return false;
-    l->MODE = 3;
   }
   // BatchNorm + activation of the input inside this launch (conv_bn.h, BnXf): forward-with-statistics launches only
   const bool xf = d0.xf != nullptr;
-  if (xf && (l->MODE != 1 || bn)) return false;
+  if (xf && l->MODE != 1) return false;
   l->XF = xf ? 1 : 0;
   l->lds = l->NBUF * tpix * K * 2 + (xf ? 2 * K * 4 : 0);
   if (l->lds > 160 * 1024) return false;
@@ -147,12 +118,8 @@ static bool c1s_fill(const mi_conv_desc* ds, int n, C1Launch* l, const mi_bn_job
   k.npix = (int)npix;
   k.ragged = ragged ? 1 : 0;
   k.nco = nco;
-  // persistent grid: as many blocks as are resident at once (LDS-limited, at most 2 per CU), never more than tiles
-  int per_cu = (160 * 1024) / l->lds;
-  if (per_cu > 1) per_cu = 1;   // (measured: two blocks per CU lose 0.5 % of the step - twice the statistics atomics, no gain in bandwidth)
-  if (per_cu < 1) per_cu = 1;
-  static const int ovr = getenv("MI_C1S_PERCU") ? atoi(getenv("MI_C1S_PERCU")) : 0;
-  if (ovr > 0 && !bn) per_cu = ovr;   // (MODE 3: the grid barrier needs every block resident - one per CU always is)
+  // persistent grid: one block per CU, never more than tiles
+  const int per_cu = 1;   // (measured: two blocks per CU lose 0.5 % of the step - twice the statistics atomics, no gain in bandwidth)
   int nb = (c1s_cus() * per_cu) / nco;
   if (nb > k.ntiles) nb = k.ntiles;
   if (nb < 1) nb = 1;
@@ -175,13 +142,10 @@ static bool c1s_fill(const mi_conv_desc* ds, int n, C1Launch* l, const mi_bn_job
       s.stats = d.stats_acc ? d.stats_acc + (size_t)c * 2 : nullptr;
       s.sld = d.CoutPad * 2;
       s.nslots = nsl;
-      s.bnj = j;
-      s.c0 = c;
       s.bias = d.bias ? d.bias + c : nullptr;
       s.aux = (d.flags & (MI_CONV_ADDRELU | MI_CONV_RELUMASK)) ? (const __bf16*)d.bn_y + c : nullptr;
       s.ldaux = d.bn_ldy;
     }
-    if (bn && !cbn_from_job(d, bn[j], &k.bn[j])) return false;
   }
   return true;
 }
@@ -190,7 +154,6 @@ static int c1s_run(const C1Launch& l, hipStream_t s) {
   switch (l.MODE) {
     case 0: return c1s_launch_mode0(l, s);
     case 1: return l.XF ? c1s_launch_mode1x(l, s) : c1s_launch_mode1(l, s);
-    case 3: return c1s_launch_mode3(l, s);
     case 4: return c1s_launch_mode4(l, s);
     case 5: return c1s_launch_mode5(l, s);
     case 6: return c1s_launch_mode6(l, s);
@@ -211,10 +174,10 @@ static bool c1s_launch_any(const mi_conv_desc* ds, int n, hipStream_t s, int* rc
     // more output channels than one launch's slice table holds (ResNet conv3 / shortcut: 1024, 2048): 512 at a time, each
     // launch streaming the (4 - 16 x smaller) input again.  All or nothing: the first chunk decides
     const int step = 32 * C1_MAX_SLICES;
-    if (!c1s_fill(ds, 1, &l, nullptr, 0, step)) return false;
+    if (!c1s_fill(ds, 1, &l, 0, step)) return false;
     *rc = c1s_run(l, s);
     for (int c = step; c < ds[0].Cout && *rc == MI_OK; c += step) {
-      if (!c1s_fill(ds, 1, &l, nullptr, c, step)) { *rc = MI_EINVAL; break; }
+      if (!c1s_fill(ds, 1, &l, c, step)) { *rc = MI_EINVAL; break; }
       *rc = c1s_run(l, s);
     }
     return true;
@@ -231,11 +194,9 @@ bool c1s_try_route(const mi_conv_desc* d) {
   if (!c1s_enabled()) return false;
   C1Launch l;
   const int step = 32 * C1_MAX_SLICES;
-  if (d->Cout > step && d->Cout % step == 0 && !d->stats_acc && !d->xf) return c1s_fill(d, 1, &l, nullptr, 0, step);
+  if (d->Cout > step && d->Cout % step == 0 && !d->stats_acc && !d->xf) return c1s_fill(d, 1, &l, 0, step);
   return c1s_fill(d, 1, &l);
 }
-bool c1s_try_plan_bn(const mi_conv_desc* ds, const mi_bn_job* bn, int n, C1Launch* l) { return c1s_enabled() && c1s_fill(ds, n, l, bn); }
-int c1s_barrier_status(unsigned* flag) { return c1s_bar_status(flag); }
 int c1s_run_planned(const C1Launch* l, hipStream_t s) { return c1s_run(*l, s); }
 
 extern "C" int mi_conv1x1_stream(const mi_conv_desc* descs, int n, mi_stream_t st) {

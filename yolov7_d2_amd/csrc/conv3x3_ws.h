@@ -20,9 +20,7 @@
 //     sums per lane (in registers, or parked in LDS between tiles where the weights leave no room), one set of fp64 atomics
 //     per block (conv_bn.h, cbn_block_stats).
 // A launch carries up to 8 jobs (the head's three levels x two towers run as one launch); a block belongs to one job.
-// MODE 0: plain, 1: + BatchNorm statistics, 2: y += result, 3: MODE 1 and then, behind a grid barrier, BatchNorm(train) +
-// SiLU (+ residual) of the block's own output tiles (conv_bn.h; see conv1x1_stream.h MODE 3): conv2 + bn + act + shortcut
-// of a Bottleneck (layers/wrappers.py:119-123) in one launch.
+// MODE 0: plain, 1: + BatchNorm statistics, 2: y += result.  (No MODE 3, as in conv1x1_stream.h.)
 // XF 1 (with MODE 1): the job's input x is the RAW output of the producing convolution; the BatchNorm(train) + SiLU that
 // BaseConv applies to it (wrappers.py:76-83) runs here, on the halo in LDS, by the wave that fetched the piece (conv_bn.h,
 // BnXf): no bn_act_fwd launch, y is read once instead of y + a; the writer job stores the activated interior pixels.
@@ -57,8 +55,7 @@ struct W3Job {
   int wld, nslots, sld, pad_;
   int tw[9];                                       // weight slab of tap position t = (dy + 1) * 3 + (dx + 1)
   int inH;                                         // input map height (= H for stride 1; input width = inW)
-  CBnFwd bn;                                       // MODE 3
-  int inW, xfw;                                    // xfw: this job stores the activated input (XF launches; one job per input tensor)
+  int inW, xfw;                                   // xfw: this job stores the activated input (XF launches; one job per input tensor)
   const BnXf* xf;                                  // XF launches: the BatchNorm + activation of this job's INPUT (device record)
 };
 struct W3K {
@@ -73,7 +70,6 @@ struct W3Launch {
 #define W3_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
 static __device__ uint4 g_w3_zero_page[4];
-static __device__ __attribute__((aligned(256))) unsigned g_w3_bar[MI_BN_BAR_WORDS];   // grid barrier of the MODE 3 launches (one at a time)
 
 __device__ __forceinline__ void w3_glds16(const void* g, unsigned lds_off) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_off) : "memory");
@@ -117,13 +113,7 @@ __global__ __launch_bounds__(WM* WN * 64, (K == 128 || (S == 2 && K == 64)) ? 1 
   const W3Job& jb = p.j[ji];
   const int b = (int)blockIdx.x - jb.blk0, nb = jb.nblk;
   const int nt = (jb.ntiles - b + nb - 1) / nb;
-  constexpr bool STATS = MODE == 1 || MODE == 3;
-  unsigned gen0 = 0;   // thread 0 only: the barrier generation this launch starts in
-  if constexpr (MODE == 3) {
-    const int nblk = (int)gridDim.x;
-    if (tid == 0)
-      gen0 = __hip_atomic_load(bn_bar_gen(g_w3_bar, (int)blockIdx.x % (nblk < BN_BAR_G ? nblk : BN_BAR_G)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  constexpr bool STATS = MODE == 1;
   // every job field the tile loop needs, in registers: behind the "memory"-clobbering DMA statements the compiler would
   // re-load them from the argument segment, and each such s_load is followed by lgkmcnt(0) - which also drains the LDS
   // fragment reads in flight (20 pipeline drains per tile)
@@ -414,54 +404,6 @@ __global__ __launch_bounds__(WM* WN * 64, (K == 128 || (S == 2 && K == 64)) ? 1 
     cbn_block_stats<WM, WN>(s1, s2, (float*)smem, wave, lane, (p.dbg & 1) != 0, [&](const int c) {
       return jb.stats + (size_t)((int)blockIdx.x % jb.nslots) * jb.sld + c * 2;
     });
-  }
-  if constexpr (MODE == 3) {
-    // ---- phase 2: every block's sums are in; BatchNorm + activation (+ residual) of this block's own tiles
-    // (no static LDS: the ring may use the whole dynamic limit; the tile buffers are dead by now, red[] sits below 16 KB)
-    int* const s_gave_up = (int*)(smem + 16384);
-    bn_grid_barrier(g_w3_bar, gen0, (int)blockIdx.x, (int)gridDim.x, s_gave_up);
-    const float poison = *s_gave_up ? __builtin_nanf("") : 0.f;   // (a timed-out wait: the sums are incomplete)
-    const CBnFwd& bn = jb.bn;
-    float scl, shl;   // of channel wm * 32 + l31
-    cbn_finalize(bn, jb.stats + (wm * 32 + l31) * 2, jb.sld, jb.nslots, wm * 32 + l31, b == 0 && wn == 0 && h == 0, poison, scl, shl);
-    float sc[2][8], sh[2][8];   // this lane's channels wm * 32 + 16 pr + 8 h + e
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        sc[pr][e] = __shfl(scl, pr * 16 + h * 8 + e, 64);
-        sh[pr][e] = __shfl(shl, pr * 16 + h * 8 + e, 64);
-      }
-    const int act = bn.act;
-    const bool has_res = bn.res != nullptr;
-    const size_t ldab = (size_t)bn.lda * 2, ldrb = (size_t)bn.ldres * 2;
-    char* const abase = (char*)bn.a + wm * 64 + h * 16;
-    const char* const rbase = (const char*)bn.res + wm * 64 + h * 16;
-    for (int i = 0; i < nt; ++i) {
-      const Org o = tile_origin(i);
-      u32x4 v[NST], r[NST];
-      size_t pixi[G];
-      bool ok[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const int py = o.ty0 + (wn * G + g) * 2 + lg, px = o.tx0 + lidx;
-        ok[g] = (py < H) & (px < Wd);
-        pixi[g] = ((size_t)o.img * H + py) * Wd + px;
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-          v[g * 2 + pr] = r[g * 2 + pr] = u32x4{0u, 0u, 0u, 0u};
-          if (ok[g]) {
-            v[g * 2 + pr] = *(const u32x4*)(ybase + pixi[g] * (size_t)ldyb + wm * 64 + h * 16 + pr * 32);
-            if (has_res) r[g * 2 + pr] = *(const u32x4*)(rbase + pixi[g] * ldrb + pr * 32);
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr)
-          if (ok[g]) *(u32x4*)(abase + pixi[g] * ldab + pr * 32) = cbn_apply8(v[g * 2 + pr], sc[pr], sh[pr], act, has_res, r[g * 2 + pr]);
-    }
   }
 }
 

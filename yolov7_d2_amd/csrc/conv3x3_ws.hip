@@ -10,10 +10,6 @@ int w3_launch_mode0(const W3Launch& l, hipStream_t s);
 int w3_launch_mode1(const W3Launch& l, hipStream_t s);
 int w3_launch_mode1x(const W3Launch& l, hipStream_t s);
 int w3_launch_mode2(const W3Launch& l, hipStream_t s);
-int w3_launch_mode3(const W3Launch& l, hipStream_t s);
-int w3_mode3_blocks_per_cu(int K, int lds);
-int w3_bar_status(unsigned* flag);
-bool cbn_from_job(const mi_conv_desc& d, const mi_bn_job& j, CBnFwd* o);   // conv1x1_stream.hip
 
 static int w3_cus() {
   static int cus = 0;
@@ -60,20 +56,18 @@ static bool w3_desc_ok(const mi_conv_desc* d, int* tw) {
   return seen == 0x1ff;
 }
 
-// bn (may be NULL): the BatchNorm jobs of the n convolutions -> MODE 3
-static bool w3_fill(const mi_conv_desc* ds, int n, W3Launch* l, const mi_bn_job* bn = nullptr) {
+static bool w3_fill(const mi_conv_desc* ds, int n, W3Launch* l) {
   if (n < 1 || n > W3_MAX_JOBS) return false;
   memset(l, 0, sizeof(*l));
   const int K = ds[0].K8 * 8, S = ds[0].in_stride;
-  if (bn && ((ds[0].flags & MI_CONV_ACCUM) || !ds[0].stats_acc || S != 1)) return false;
-  const int mode = (ds[0].flags & MI_CONV_ACCUM) ? 2 : (ds[0].stats_acc ? (bn ? 3 : 1) : 0);
+  const int mode = (ds[0].flags & MI_CONV_ACCUM) ? 2 : (ds[0].stats_acc ? 1 : 0);
   // BatchNorm + activation of the INPUT inside this launch (conv_bn.h, BnXf): forward-with-statistics launches only, every
   // job carries its record (jobs over one input tensor share it; exactly one of them has xf_write)
   const bool xf = ds[0].xf != nullptr;
   if (xf && mode != 1) return false;
   const int TH = w3_tile_h(S, K);
   const int hrows = ((S == 1 ? (TH + 2) * (W3_TW + 2) : (2 * TH + 1) * (2 * W3_TW + 1)) + 63) / 64 * 64;
-  const int lds = 2 * (K / 8) * hrows * 16 + ((mode == 1 || mode == 3) ? 256 * 32 * 4 : 0) + (xf ? 2 * K * 4 : 0);   // halo ring (+ per-lane BatchNorm sums) (+ input scale / shift)
+  const int lds = 2 * (K / 8) * hrows * 16 + (mode == 1 ? 256 * 32 * 4 : 0) + (xf ? 2 * K * 4 : 0);   // halo ring (+ per-lane BatchNorm sums) (+ input scale / shift)
   long long total = 0;
   int nj = 0;
   for (int j = 0; j < n; ++j) {
@@ -97,7 +91,6 @@ static bool w3_fill(const mi_conv_desc* ds, int n, W3Launch* l, const mi_bn_job*
       jb.nslots = (d.stats_slots >= 1 && d.stats_slots <= MI_BN_SLOTS) ? d.stats_slots : MI_BN_SLOTS;
       jb.sld = d.CoutPad * 2;
       total += jb.ntiles;
-      if (bn && !cbn_from_job(d, bn[j], &jb.bn)) return false;
       jb.xf = (const BnXf*)d.xf;
       jb.xfw = (xf && d.xf_write && c0 == 0) ? 1 : 0;
     }
@@ -105,16 +98,8 @@ static bool w3_fill(const mi_conv_desc* ds, int n, W3Launch* l, const mi_bn_job*
   n = nj;
   // persistent blocks: K = 128 one per CU (288 VGPRs of weights per wave), K = 64 two, K = 32 four; shared between
   // the jobs in proportion to their tiles (every job gets at least one block, none more blocks than tiles)
-  static const int ovr = getenv("MI_W3_PERCU") ? atoi(getenv("MI_W3_PERCU")) : 0;
-  int per_cu = ovr > 0 ? ovr : (K == 128 ? 1 : (K == 64 ? 2 : 4));
-  if (S == 2 && ovr <= 0) per_cu = (160 * 1024) / lds >= 2 && K != 128 ? 2 : 1;    // (the stride-2 halo ring is 41 - 98 KB)
-  if (mode == 3) {   // the grid barrier needs every block resident
-    static int occ[3] = {-1, -1, -1};
-    int& o = occ[K == 128 ? 0 : (K == 64 ? 1 : 2)];
-    if (o < 0) o = w3_mode3_blocks_per_cu(K, lds);
-    if (o < 1) return false;
-    if (per_cu > o) per_cu = o;
-  }
+  int per_cu = K == 128 ? 1 : (K == 64 ? 2 : 4);
+  if (S == 2) per_cu = (160 * 1024) / lds >= 2 && K != 128 ? 2 : 1;    // (the stride-2 halo ring is 41 - 98 KB)
   long long cap = (long long)w3_cus() * per_cu;
   if (cap > total) cap = total;
   int used = 0;
@@ -160,7 +145,6 @@ static int w3_run(const W3Launch& l, hipStream_t s) {
   switch (l.MODE) {
     case 0: return w3_launch_mode0(l, s);
     case 1: return l.XF ? w3_launch_mode1x(l, s) : w3_launch_mode1(l, s);
-    case 3: return w3_launch_mode3(l, s);
     default: return w3_launch_mode2(l, s);
   }
 }
@@ -178,8 +162,6 @@ bool w3_try_launch(const mi_conv_desc* ds, int n, hipStream_t s, int* rc) {
   return true;
 }
 bool w3_try_plan(const mi_conv_desc* ds, int n, W3Launch* l) { return w3_enabled() && w3_fill(ds, n, l); }
-bool w3_try_plan_bn(const mi_conv_desc* ds, const mi_bn_job* bn, int n, W3Launch* l) { return w3_enabled() && w3_fill(ds, n, l, bn); }
-int w3_barrier_status(unsigned* flag) { return w3_bar_status(flag); }
 int w3_run_planned(const W3Launch* l, hipStream_t s) { return w3_run(*l, s); }
 
 extern "C" int mi_conv3x3_ws(const mi_conv_desc* descs, int n, mi_stream_t st) {

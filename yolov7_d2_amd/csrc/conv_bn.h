@@ -1,7 +1,10 @@
-// Grid-wide barrier over the resident blocks of one launch + the BatchNorm(train) + activation (+ residual) pass that a
-// persistent convolution kernel runs over ITS OWN output tiles behind that barrier (conv1x1_stream.h / conv3x3_ws.h,
-// MODE 3): the second half of BaseConv.forward (yolov7/modeling/backbone/layers/wrappers.py:76-83) without a second
-// launch.  Used by bn_act.hip (fused BatchNorm backward) and by the two convolution kernels.
+// What train-mode BatchNorm shares between bn_act.hip and the two persistent convolution kernels (conv1x1_stream.h /
+// conv3x3_ws.h):
+//   * the grid-wide barrier over the resident blocks of one launch, in two halves (bn_bar_arrive / bn_bar_finish): the
+//     one-launch BatchNorm backward of bn_act.hip (bn_bwd_fused);
+//   * CBnFwd, the record of one BatchNorm(train) forward, and cbn_apply8, its expression on 8 channels of a pixel;
+//   * cbn_block_stats, the (sum, sumsq) tail of a convolution launch with statistics (MODE 1);
+//   * BnXf / bnx_tables / bnx_apply_lds: the BatchNorm + activation of a convolution's INPUT, run by the consuming launch.
 #pragma once
 #include "common.h"
 #include "bn_common.h"
@@ -21,7 +24,7 @@ __device__ __forceinline__ unsigned* bn_bar_cnt(unsigned* bar, int g) { return b
 // acknowledged when the block passes its __syncthreads (workgroup release = s_waitcnt vmcnt(0)), and read back after the
 // barrier by agent-scope atomic loads, which bypass the non-coherent caches.
 // *gave_up (LDS) = 1 when this block's wait timed out: its sums are incomplete and it must poison what it writes.
-// thread 0 of a block: the three steps the barrier forms below are composed of
+// thread 0 of a block: the three steps the two barrier halves below are composed of
 __device__ __forceinline__ int bn_bar_group(const int bid, const int nb) { return bid % (nb < BN_BAR_G ? nb : BN_BAR_G); }
 // count this block's arrival; true for the block that arrives last of all (it has reset the counters for the next launch)
 __device__ __forceinline__ bool bn_bar_count(unsigned* bar, const int bid, const int nb) {
@@ -55,18 +58,7 @@ __device__ __forceinline__ bool bn_bar_wait(unsigned* bar, const unsigned gen0, 
   return false;
 }
 
-__device__ __forceinline__ void bn_grid_barrier(unsigned* bar, const unsigned gen0, const int bid, const int nb, int* gave_up) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (see bn_bar_arrive)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    *gave_up = 0;
-    if (bn_bar_count(bar, bid, nb)) bn_bar_release(bar, nb);
-    else if (bn_bar_wait(bar, gen0, bid, nb)) *gave_up = 1;
-  }
-  __syncthreads();
-}
-
-// The same barrier in two halves, so that the block that arrives LAST can do work for everybody before it releases the
+// The barrier in two halves, so that the block that arrives LAST can do work for everybody before it releases the
 // others (bn_bwd_fused: it folds the accumulator slots into one total per channel - one block's worth of loads instead of
 // every block's; see bn_act.hip).  *is_last / *gave_up live in LDS.
 __device__ __forceinline__ void bn_bar_arrive(unsigned* bar, const int bid, const int nb, int* gave_up, int* is_last) {
@@ -91,8 +83,7 @@ __device__ __forceinline__ void bn_bar_finish(unsigned* bar, const unsigned gen0
   __syncthreads();
 }
 
-
-// ---- BatchNorm(train) forward of a convolution, phase 2 of the convolution launch
+// ---- one BatchNorm(train) forward: the record BnXf embeds (and mi_bnx mirrors)
 struct CBnFwd {
   const __bf16* res;   // residual added after the activation (Bottleneck shortcut) or NULL
   __bf16* a;           // activated output
@@ -109,37 +100,6 @@ struct CBnFwd {
   double inv_count, unbias;
   float eps, momentum;
 };
-
-// channel c's (scale, shift) from ITS fp64 accumulators acc[slot * sld + {0, 1}] (acc points at the channel): bn_moments /
-// bn_record of bn_common.h, as at every other site.  Agent-scope loads: the sums were added memory-side by every block.
-// `writer`: this lane also records scale / shift / mean / invstd and updates the running statistics (one lane per channel
-// of the launch); `poison` (NaN after a barrier timeout, else 0) marks results computed from incomplete sums.
-__device__ __forceinline__ void cbn_finalize(const CBnFwd& bn, const double* acc, int sld, int nslots, int c, bool writer,
-                                             float poison, float& sc_out, float& sh_out) {
-  double v1[MI_BN_SLOTS], v2[MI_BN_SLOTS];
-#pragma unroll
-  for (int k = 0; k < MI_BN_SLOTS; ++k) {
-    if (k < nslots) {
-      v1[k] = __hip_atomic_load(acc + (size_t)k * sld, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      v2[k] = __hip_atomic_load(acc + (size_t)k * sld + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      v1[k] = v2[k] = 0.0;
-    }
-  }
-  double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < MI_BN_SLOTS; ++k) {
-    s1 += v1[k];
-    s2 += v2[k];
-  }
-  float sc, sh;
-  const BnMoments m = bn_moments(s1, s2, bn.inv_count, bn.eps, bn.gamma[c], bn.beta[c], sc, sh);
-  sc += poison;
-  sh += poison;
-  sc_out = sc;
-  sh_out = sh;
-  if (writer) bn_record<true>(bn, c, sc, sh, m, poison);
-}
 
 // 8 channels of one pixel: a = act(y * scale + shift) (+ res), the expression of bn_act_fwd_body
 __device__ __forceinline__ u32x4 cbn_apply8(const u32x4 yv, const float* sc, const float* sh, const int act, const bool has_res,
@@ -159,7 +119,7 @@ __device__ __forceinline__ u32x4 cbn_apply8(const u32x4 yv, const float* sc, con
 }
 
 // ---- the block's BatchNorm (sum, sumsq) of a persistent convolution launch: the tail behind the tile loop of c1s_kernel /
-// w3_kernel (MODE 1, 3, XF).  Every lane arrives with 16 channels x (sum, sumsq) over ITS pixels: lane (l31, h) of wave
+// w3_kernel (MODE 1, XF).  Every lane arrives with 16 channels x (sum, sumsq) over ITS pixels: lane (l31, h) of wave
 // (wm, wn) holds channel wm * 32 + 8 (r >> 2) + 4 h + (r & 3) in register r (the MFMA accumulator order).
 // value of lane (lane ^ OFF), OFF < 32: DPP where gfx950 has a form with these operands (quad_perm for 1 and 2, a rotation
 // by half a row for 8), ds_bpermute for 4 and 16.  Called with every lane active.
@@ -257,7 +217,7 @@ static_assert(sizeof(BnXf) == sizeof(mi_bnx) && __builtin_offsetof(BnXf, acc) ==
               __builtin_offsetof(BnXf, bn.lda) == __builtin_offsetof(mi_bnx, lda), "mi_bnx (include/mi355_det.h) mirrors BnXf");
 // every block: (scale, shift) of all C input channels into LDS tables - the arithmetic of bn_fwd_prologue (bn_common.h) with
 // ITS loads: plain 16-byte loads, thread c next to thread c + 1 (the sums were completed by the previous launch;
-// cbn_finalize's agent-scope 8-byte atomic loads are for readers BEHIND a grid barrier and cost one L2 request each: with
+// agent-scope 8-byte atomic loads are for readers BEHIND a grid barrier and cost one L2 request each: with
 // every block of a launch asking for the same C x nslots x 16 bytes they took ~9 us of a 512-channel 20x20 launch).
 // `rec`: this block also records scale / shift / mean / invstd for the backward pass and updates the running statistics
 __device__ __forceinline__ void bnx_tables(const BnXf* __restrict__ xf, float* s_sc, float* s_sh, const int nthreads, const bool rec) {

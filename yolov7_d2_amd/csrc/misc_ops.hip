@@ -804,7 +804,7 @@ __global__ __launch_bounds__(128) void colsum_wide_stage2_kernel(const float* __
 }
 // one launch: stage 1 as above, then the LAST block of each 64-channel chunk to arrive (a counter per chunk) sums the chunk's
 // partials in block order - deterministic, and no second launch (143 bias gradients per DETR step).  The partials cross
-// blocks as agent-scope atomic stores / loads (performed memory-side: no cache maintenance needed, cf. bn_grid_barrier).
+// blocks as agent-scope atomic stores / loads (performed memory-side: no cache maintenance needed, cf. the grid barrier of conv_bn.h).
 // The counters are a library-wide static: launches of this kernel must not overlap (they are issued on one stream).
 #define COLSUM_MAX_CHUNKS 64
 static __device__ unsigned g_colsum_cnt[COLSUM_MAX_CHUNKS];

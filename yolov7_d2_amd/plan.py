@@ -743,12 +743,6 @@ class Plan:
         where the trainer reads the losses anyway."""
         if self.b.device.type != "cuda":
             return
-        if any(getattr(c, "fused_bn", False) for c in getattr(self, "fwd_list", [])):
-            fl = C.c_uint32(0)
-            L.check(L.lib().mi_conv_bn_barrier_status(C.byref(fl)), "conv_bn_barrier_status")
-            if fl.value:
-                raise L.MI355Error(f"conv + BatchNorm grid barrier timed out (kernel families {fl.value:#x}): a block was not "
-                                   "resident (another kernel holds CUs?); set MI_CONV_BN_FUSE=0")
         bars = [bf for bf in self.b.bufs if bf.name.endswith(".bar")]
         if not bars:
             return
@@ -1167,66 +1161,6 @@ class Plan:
         g.members = list(cs)
         return g
 
-    def _fuse_conv_bn(self, cmds):
-        """CONV (+ BatchNorm statistics) directly followed by the train-mode BN_ACT_FWD of its output - or a CONV_GROUP
-        followed by the BN_GROUP of the same layers - becomes ONE launch when the convolutions run on the persistent
-        streaming 1x1 / weight-stationary 3x3 kernels: the BatchNorm pass is their second phase behind a grid barrier
-        (mi_conv2d_bn_plan).  The whole BaseConv.forward of backbone/layers/wrappers.py:76-83 and the Bottleneck shortcut
-        add in one command.  OPT-IN (MI_CONV_BN_FUSE=1): measured on the YOLOX-s step (same box, graphs on) the 41 fused
-        launches are 1.7 % SLOWER than the 82 separate ones (5.698 vs 5.600 ms) although they are 2 % faster when each
-        command is timed alone: a launch inside the hipGraph costs ~1-2 us, less than the barrier + the statistics read-back
-        behind it, and the second phase streams with the convolution kernel's 4-8 waves per CU instead of the BatchNorm
-        kernel's 16+ (profiles/r03_conv_bn_fused_ab.txt)."""
-        if os.environ.get("MI_CONV_BN_FUSE", "0") != "1" or self.b.device.type != "cuda":
-            return cmds
-        CONV, CONVG, BNF, BNG = L.OP["CONV"], L.OP["CONV_GROUP"], L.OP["BN_ACT_FWD"], L.OP["BN_GROUP"]
-        lib = L.lib()
-        maxpix = int(os.environ.get("MI_CONV_BN_FUSE_MAXPIX", "0"))
-        out, k = [], 0
-        while k < len(cmds):
-            c = cmds[k]
-            nxt = cmds[k + 1] if k + 1 < len(cmds) else None
-            convs = bns = None
-            if nxt is not None and c.op == CONV and nxt.op == BNF:
-                convs, bns = [c], [nxt]
-            elif nxt is not None and c.op == CONVG and nxt.op == BNG and nxt.i[0] == 0 and len(c.members) == len(nxt.members):
-                convs, bns = c.members, nxt.members
-            g = None
-            # MI_CONV_BN_FUSE_MAXPIX=n: only layers whose maps have <= n pixels per image (1600 = the 40x40 / 20x20 sub-network,
-            # where a launch is mostly fixed cost and the second phase has little to stream)
-            if convs is not None and maxpix and any(cv.desc.outH * cv.desc.outW > maxpix for cv in convs):
-                convs = None
-            if convs is not None and all(b_.p[1].resolve() for b_ in bns):      # (train mode: the jobs carry accumulators)
-                n = len(convs)
-                descs = (L.mi_conv_desc * n)()
-                for d, cv in zip(descs, convs):
-                    t = self._make_desc(cv.desc)
-                    self.descs.pop()
-                    C.memmove(C.byref(d), C.byref(t), C.sizeof(L.mi_conv_desc))
-                jobs = (L.mi_bn_job * n)()
-                for j, bc in zip(jobs, bns):
-                    self._fill_bn_fwd_job(j, bc)
-                # the BatchNorm job of position j must belong to convolution j (lanes are issued in the same order)
-                if all(d.y == j.y for d, j in zip(descs, jobs)):
-                    meta = L.mi_conv_group()
-                    rc = lib.mi_conv2d_bn_plan(descs, jobs, n, C.byref(meta))
-                    if rc < 0:
-                        lib.mi_last_error()
-                    elif rc == 1:
-                        self.descs += [meta, descs, jobs]
-                        g = _Cmd(CONVG, p=[_Ptr(C.addressof(meta)), _Ptr(0)], tag=c.tag + "+" + nxt.tag)
-                        g.group_descs = list(descs)
-                        g.members = list(convs) + list(bns)
-                        g.fused_bn = True
-                        g.bn_jobs = list(jobs)
-            if g is not None:
-                out.append(g)
-                k += 2
-            else:
-                out.append(c)
-                k += 1
-        return out
-
     # ---------------------------------------------------------------- BatchNorm + SiLU in the consumer
     @staticmethod
     def _cmd_bufs(c):
@@ -1266,7 +1200,7 @@ class Plan:
         own lists are not touched (tests/plan_interp.py keeps interpreting BaseConv as conv, BatchNorm, conv)."""
         self.deferred_bn = []
         mode = os.environ.get("MI_BN_IN_CONSUMER", "auto")
-        if mode == "0" or not self.b.bn_train or os.environ.get("MI_CONV_BN_FUSE", "0") == "1":
+        if mode == "0" or not self.b.bn_train:
             return cmds
 
         def pays(sp, x):
@@ -1365,7 +1299,7 @@ class Plan:
 
         for c in cmds:
             refs = self._cmd_bufs(c)
-            if c.op in (CONV, CONVG) and not getattr(c, "fused_bn", False) and pending:
+            if c.op in (CONV, CONVG) and pending:
                 got = try_convert(c)
                 if got is not None:
                     res, picks = got
@@ -1415,7 +1349,7 @@ class Plan:
     def _materialize(self, cmds, which):
         cmds = self._group_lanes(self._group_parity(cmds))
         if which == "fwd":
-            cmds = self._fuse_conv_bn(self._defer_bn(cmds))
+            cmds = self._defer_bn(cmds)
         arr = (L.mi_cmd * max(1, len(cmds)))()
         tags = []
         if which == "fwd":
