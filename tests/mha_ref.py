@@ -90,15 +90,14 @@ def bf(x):
 Emu = collections.namedtuple("Emu", "O O32 lse delta dq dk dv")
 
 
-def emulate_kernel(q, k, v, dout, mask, scale, H, keep=None, drop_scale=1.0, o32=True, version=2):
+def emulate_kernel(q, k, v, dout, mask, scale, H, keep=None, drop_scale=1.0, o32=True):
     """fp32 restatement of the kernels' arithmetic with their bf16 rounding points (read off csrc/mha.hip; the backward's are
     the ones tools/attn_bwd_error.py writes down): P (after keep drop_scale) before P V, the normaliser from exactly those
-    bf16 weights (no dropout, version 2) or from the fp32 weights before the drop; O stored bf16 and, separately, fp32; delta
-    from the fp32 or the bf16 O; P recomputed from the saved lse; dS before its two products (version 2: without scale, which
-    multiplies the accumulators; version 1: with it); dq, dk, dv stored bf16.  Version 2 works in the exp2 domain on chunks
-    of 128 keys with the LAZY reference maximum (it moves when some score of a 16-query wave exceeds it by more than
-    8 / (scale log2 e)); version 1 on 32-key tiles with the true running maximum.  fp32 sums are taken in torch's order, not
-    the MFMA's: the exact cases do not depend on it, the bounds of the numerics tests cover it."""
+    bf16 weights (no dropout) or from the fp32 weights before the drop; O stored bf16 and, separately, fp32; delta from the
+    fp32 or the bf16 O; P recomputed from the saved lse; dS before its two products (without scale, which multiplies the
+    accumulators); dq, dk, dv stored bf16.  The kernels work in the exp2 domain on chunks of 128 keys with the LAZY reference
+    maximum (it moves when some score of a 16-query wave exceeds it by more than 8 / (scale log2 e)).  fp32 sums are taken
+    in torch's order, not the MFMA's: the exact cases do not depend on it, the bounds of the numerics tests cover it."""
     f32 = torch.float32
     Q, K, V, DO = (heads(t.to(f32), H) for t in (q, k, v, dout))
     B, _, Lq, _ = Q.shape
@@ -122,30 +121,22 @@ def emulate_kernel(q, k, v, dout, mask, scale, H, keep=None, drop_scale=1.0, o32
     oacc = torch.zeros(B, H, Lp, D, dtype=f32, device=dev)
     lacc = torch.zeros(B, H, Lp, dtype=f32, device=dev)
     one, zero = torch.ones((), dtype=f32, device=dev), torch.zeros((), dtype=f32, device=dev)
-    step = KC if version == 2 else 32
+    step = KC
     for k0 in range(0, Lk, step):
         s = Sp[..., k0:k0 + step]
-        if version == 1:
-            s = s * scale_t
         mx = s.amax(-1)
-        if version == 2:
-            trig = (mx > m_run + 8.0 / sc2).view(B, H, G, 16).any(-1, keepdim=True).expand(B, H, G, 16).reshape(B, H, Lp)
-        else:
-            trig = torch.ones_like(mx, dtype=torch.bool)
+        trig = (mx > m_run + 8.0 / sc2).view(B, H, G, 16).any(-1, keepdim=True).expand(B, H, G, 16).reshape(B, H, Lp)
         m_new = torch.where(trig, torch.maximum(m_run, mx), m_run)
         none = m_new == NEG
         dm = torch.where(none, zero, m_run - torch.where(none, zero, m_new))
-        alpha = torch.where(trig & ~none, torch.exp2(dm * (sc2 if version == 2 else LOG2E_F)), one)
+        alpha = torch.where(trig & ~none, torch.exp2(dm * sc2), one)
         m_run = m_new
         mz = torch.where(none, zero, m_new)
-        if version == 2:
-            pe = torch.exp2(s * sc2 + (-mz * sc2)[..., None])
-        else:
-            pe = torch.exp2((s - mz[..., None]) * LOG2E_F)
+        pe = torch.exp2(s * sc2 + (-mz * sc2)[..., None])
         pe = pe * ~none[..., None]
         pf = bf(pe * (ksp[..., k0:k0 + step] if drop else ks))
         oacc = oacc * alpha[..., None] + pf @ V[:, :, k0:k0 + step]
-        lacc = lacc * alpha + (pf.sum(-1) if (version == 2 and not drop) else pe.sum(-1))
+        lacc = lacc * alpha + (pe.sum(-1) if drop else pf.sum(-1))
     oacc, lacc, m_run = oacc[:, :, :Lq], lacc[:, :, :Lq], m_run[:, :, :Lq]
     some = lacc > 0
     inv = torch.where(some, 1.0 / torch.where(some, lacc, one), zero)
@@ -153,26 +144,18 @@ def emulate_kernel(q, k, v, dout, mask, scale, H, keep=None, drop_scale=1.0, o32
     O = bf(O32)
     ml = torch.where(some, m_run, zero)
     ll = torch.log2(torch.where(some, lacc, one))
-    lse = torch.where(some, (ml * sc2 + ll) * LN2_F if version == 2 else ml + ll * LN2_F, torch.full_like(ml, NEG))
+    lse = torch.where(some, (ml * sc2 + ll) * LN2_F, torch.full_like(ml, NEG))
     # ---- backward
     delta = (DO * (O32 if o32 else O)).sum(-1)
     lz = torch.where(some, lse, zero)
-    if version == 2:
-        pe = torch.exp2(Sraw * sc2 + (-lz * LOG2E_F)[..., None])
-    else:
-        pe = torch.exp2((Sraw * scale_t - lz[..., None]) * LOG2E_F)
+    pe = torch.exp2(Sraw * sc2 + (-lz * LOG2E_F)[..., None])
     pe = pe * some[..., None]
     dp = DO @ V.transpose(-1, -2)
     ds = pe * (dp * ks - delta[..., None])
     pf = bf(pe * ks)
-    if version == 2:
-        ds = bf(ds)
-        dq = bf((ds @ K) * scale_t)
-        dk = bf((ds.transpose(-1, -2) @ Q) * scale_t)
-    else:
-        ds = bf(ds * scale_t)
-        dq = bf(ds @ K)
-        dk = bf(ds.transpose(-1, -2) @ Q)
+    ds = bf(ds)
+    dq = bf((ds @ K) * scale_t)
+    dk = bf((ds.transpose(-1, -2) @ Q) * scale_t)
     dv = bf(pf.transpose(-1, -2) @ DO)
     return Emu(rows(O), rows(O32), lse, delta, rows(dq), rows(dk), rows(dv))
 
@@ -309,26 +292,14 @@ def exact_cases(ncu=256):
     return sweep, ex
 
 
-def v1_cases():
-    """the version-1 kernels (MI_MHA_V2=0, run in a child process): each family on more than one 32-key tile, a ragged
-    64-query block, a fully masked image, the packed and a wide stride, with and without o_f32"""
-    out = []
-    for fi, fam in enumerate(("uniform", "gather", "dropout")):
-        sc = 64.0 if fam == "gather" else 0.5
-        out += [Case(f"v1-{fam}-a", fam, 2, 8, 150, 300, _live(fam, 2, 300), "q", sc, True, "wide", False, 2000 + fi),
-                Case(f"v1-{fam}-b", fam, 3, 3, 91, 91, _live(fam, 3, 91, 1), "k", sc, False, "packed", True, 2010 + fi)]
-    return out
-
-
 def mutation_cases():
-    """where the mutants are judged (version 2; version 1 in the child): Lk = 16 g + 1, so that the ragged last group of the
+    """where the mutants are judged: Lk = 16 g + 1, so that the ragged last group of the
     dK/dV kernel is one key - the smallest thing it can leave unwritten - and B x H x Lq = 63200 query rows, so that one wholly
     wrong row (the gather family's dropped key) is 0.6 % of the output's norm"""
     out = []
     for fi, fam in enumerate(("uniform", "gather", "dropout")):
         sc = 64.0 if fam == "gather" else 0.5
-        out += [Case(f"mut-{fam}", fam, 5, 32, 395, 193, _live(fam, 5, 193), "q", sc, True, "E", False, 3000 + fi),
-                Case(f"v1-mut-{fam}", fam, 5, 32, 395, 161, _live(fam, 5, 161), "q", sc, True, "wide", False, 3010 + fi)]
+        out += [Case(f"mut-{fam}", fam, 5, 32, 395, 193, _live(fam, 5, 193), "q", sc, True, "E", False, 3000 + fi)]
     return out
 
 
@@ -478,12 +449,12 @@ def reference_of(c, ops, keep=None, forward_only=False, kill=None, mask=None, de
                                kill=d(kill))
 
 
-def emulation_of(c, ops, keep=None, forward_only=False, version=2, device="cpu"):
+def emulation_of(c, ops, keep=None, forward_only=False, device="cpu"):
     v = ops.v_fwd if forward_only else ops.v
     d = lambda t: None if t is None else t.to(device)
     return emulate_kernel(d(ops.q), d(ops.k), d(v), d(ops.dout), d(ops.mask), c.scale, c.H,
                           keep=d(keep) if c.family == "dropout" else None, drop_scale=2.0 if c.family == "dropout" else 1.0,
-                          o32=c.o32, version=version)
+                          o32=c.o32)
 
 
 # ------------------------------------------------------------------------------------------------------------ mutants

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the attention core csrc/mha.hip - forward, delta, dQ, dK/dV, their version-2 forms and the dropout template of
+"""GPU (-m gpu): the attention core csrc/mha.hip - forward, delta, dQ, dK/dV and the dropout template of
 each - against the plain float64 reference of tests/mha_ref.py with NO tolerance, through the C ABI (mi_mha_fwd_dropout_ld /
 mi_mha_bwd_dropout_ld; the tests own scale, H, the row strides and the o_f32 / lse pointers), on every route and block shape.
 
@@ -20,13 +20,8 @@ with NaN and every element must have been written; the input buffers hold NaN ou
 
 Coverage is counted: the version-2 block shape (mha2_waves: 4 .. 12 waves of 16 rows, from L, B x H and the CU count) is
 mirrored in Python (mha_ref.mirror_waves) and the sweep must give every wave count to each of the three version-2 kernels in
-both template forms; the version-1 kernels (MI_MHA_V2=0, read once per process) run in a child process."""
+both template forms."""
 import collections
-import json
-import os
-import subprocess
-import sys
-import time
 import types
 
 import pytest
@@ -40,7 +35,6 @@ DEV = "cuda"
 SENT = -1536.0                 # sentinel (exact in bf16, fp32 and fp64)
 GUARD = 64                     # guard elements around every buffer (128 bytes of bf16: the 16-byte alignments hold)
 NAN = float("nan")
-CHILD_TIMEOUT = 120            # seconds; the child measured 3 s on an MI355X, most of it starting torch (see the test)
 
 
 def ncu():
@@ -194,10 +188,6 @@ def run_case(c, seen=None, want_result=False):
     return bad
 
 
-def _v2_here():
-    assert os.environ.get("MI_MHA_V2", "1") != "0", "this process must run the version-2 kernels (MI_MHA_V2 is read once)"
-
-
 def test_wave_mirror_by_the_grid_arithmetic():
     """mha_ref.mirror_waves restates mha2_waves; what can be held to the launcher without reading its mind is its grid
     arithmetic: 4 .. 12 waves (a block of at most 768 threads, the kernels' launch bound), blocks x waves cover every 16-row
@@ -222,7 +212,6 @@ def test_exact_on_every_block_shape(family):
     """nine cases at B x H = 5 x 32 whose Lq and Lk (none a multiple of 16, ragged last blocks, three key chunks, scattered /
     leading / whole-chunk masks, a fully masked image in every second one, q or k zero in turn, all four stride forms, with
     and without o_f32) give the forward and dQ kernels (by Lq) and dK/dV (by Lk) every wave count 4 .. 12 - counted"""
-    _v2_here()
     sweep, _ = case_table(ncu())
     seen = collections.defaultdict(set)
     bad = []
@@ -239,7 +228,6 @@ def test_exact_on_small_shapes_and_parameter_variants(family):
     """L = 1; Lk < 32; Lk just above 128 and 256; the nwv > gq clamp (B x H above the CU count); H in {1, 3, 8, 32}; B in
     {1, 2, 5, ...}; no mask; a fully masked image; the packed q / k buffer and the wider strides; delta from the bf16 O
     (o_f32 = NULL); lse = NULL in a forward-only launch"""
-    _v2_here()
     _, extras = case_table(ncu())
     bad = []
     for c in extras:
@@ -254,7 +242,6 @@ def test_mutants_fail_exactly_where_the_norm_passes(family):
     dropped from one query row, the mask boundary moved by one key for one wave, one row's keep bits shifted by one element,
     one head's dv row of the ragged last group zeroed, or one lse off by 2^-6 is REJECTED by the exact comparison with the
     device's (correct) result, and ACCEPTED by the Frobenius criterion of tests/test_gpu_detr.py at the same shape"""
-    _v2_here()
     c = [m for m in R.mutation_cases() if m.name == "mut-" + family][0]
     mutants_on_device(c)
 
@@ -271,40 +258,6 @@ def mutants_on_device(c):
     if c.family == "dropout":                       # the keep bits are the device's own: one export serves reference and mutants
         keep[0] = Job(c, ops).keep
     R.check_mutants(c, ops, None if keep.get(0) is None else keep[0].cpu(), result_of, device=DEV)
-
-
-def run_version1():
-    """what the child runs: the exact families and the mutants on the version-1 kernels"""
-    bad = []
-    for c in R.v1_cases():
-        bad += run_case(c)
-    for c in R.mutation_cases():
-        if c.name.startswith("v1-"):
-            try:
-                mutants_on_device(c)
-            except AssertionError as e:
-                bad.append(f"{c.name}: {e}"[:400])
-    return bad
-
-
-def test_version1_kernels_in_a_child():
-    """MI_MHA_V2 is a function-local static read once per process, so the version-1 kernels (mha_fwd_kernel,
-    mha_bwd_dq_kernel, mha_bwd_dkv_kernel) run in a fresh child with MI_MHA_V2=0: the three families on several 32-key
-    tiles, a ragged 64-query block, a fully masked image, packed and wide strides, dropout, and the mutants.  The child took
-    3 s on an MI355X (mostly interpreter and library start-up); the limit is CHILD_TIMEOUT = 120 s.  A child that ends
-    abnormally ends the test, and nothing more is started."""
-    env = dict(os.environ, MI_MHA_V2="0")
-    t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "mha_exact_gpu_child.py")],
-                       env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    print("child wall time %.1f s" % (time.time() - t0))
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    out = json.loads(r.stdout.strip().splitlines()[-1])
-    assert out["env"] == {"MI_MHA_V2": "0"}
-    assert out["kernels"] == ["mha_fwd_kernel", "mha_delta_kernel", "mha_bwd_dq_kernel", "mha_bwd_dkv_kernel"]
-    assert out["cases"] == [c.name for c in R.v1_cases()] + [c.name for c in R.mutation_cases() if c.name.startswith("v1-")]
-    assert {f for f, _ in out["families"]} == {"uniform", "gather", "dropout"}
-    assert out["bad"] == [], out["bad"][:20]
 
 
 def test_refusals_leave_the_outputs_untouched():
@@ -351,7 +304,6 @@ def test_numerics_within_derived_bounds(nc):
     bound mha_ref.error_bounds derives from the float64 reference's own intermediates (constants 2^-8 and 2^-24, nothing
     fitted; the derivation is that function's docstring), with the hygiene of every launch.  The ratios and the median of
     bound / |value| are printed (the latter is judged in tests/test_mha_ref.py::test_bounds_are_not_vacuous)."""
-    _v2_here()
     ops = R.make_numerics_operands(nc)
     c = R.Case(nc.name, "numerics", nc.B, nc.H, nc.Lq, nc.Lk, None, "", R.NSCALE, nc.o32, "wide" if nc.seed % 2 else "E", False, nc.seed)
     d = lambda t: None if t is None else t.to(DEV)

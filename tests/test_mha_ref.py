@@ -44,7 +44,7 @@ def test_reference_is_float64_autograd(drop, H, B, Lq, Lk, scale):
 
 def test_fully_masked_rows_weigh_nothing():
     """an image whose keys are all padded: O = 0, lse = -inf, dq = 0, and its dk / dv are 0; the other images are what they
-    are without it - in the reference and in both emulated kernel versions"""
+    are without it - in the reference and in the emulated kernels"""
     g = torch.Generator().manual_seed(4)
     H, B, Lq, Lk, E = 2, 3, 20, 140, 64
     q, k, v, do = (R.bf(torch.randn(n, B, E, generator=g)).double() for n in (Lq, Lk, Lk, Lq))
@@ -53,7 +53,7 @@ def test_fully_masked_rows_weigh_nothing():
     r = R.attention_reference(q, k, v, do, mask, 0.2, H)
     sub = [0, 2]
     r2 = R.attention_reference(q[:, sub], k[:, sub], v[:, sub], do[:, sub], mask[sub], 0.2, H)
-    for res in (r, R.emulate_kernel(q, k, v, do, mask, 0.2, H, version=2), R.emulate_kernel(q, k, v, do, mask, 0.2, H, version=1)):
+    for res in (r, R.emulate_kernel(q, k, v, do, mask, 0.2, H)):
         assert bool((res.lse[1] == R.NEG).all()) and bool(torch.isfinite(res.lse[sub]).all())
         for t in (res.O, res.dq, res.dk, res.dv):
             assert float(t[:, 1].abs().max()) == 0 and bool(torch.isfinite(t).all())
@@ -84,21 +84,21 @@ def test_wave_mirror_and_case_table():
     for c in cl:                                         # ceil(gq B H / ncu) > gq >= 4: clamped to gq
         gq = -(-c.Lq // 16)
         assert -(-gq * c.B * c.H // NCU) > gq >= 4 and R.mirror_waves(c.Lq, c.B * c.H, NCU) == gq
-    assert len({c.name for c in allc + R.v1_cases()}) == len(allc) + len(R.v1_cases())
+    assert len({c.name for c in allc}) == len(allc)
     import test_gpu_mha_exact as T
     assert T.case_table(NCU) == (sweep, extras)
 
 
 def _all_cases():
     sweep, extras = R.exact_cases(NCU)
-    return sum(sweep.values(), []) + extras + R.v1_cases() + R.mutation_cases()
+    return sum(sweep.values(), []) + extras + R.mutation_cases()
 
 
 @pytest.mark.parametrize("c", _all_cases(), ids=lambda c: c.name)
 def test_conditions_hold_and_emulation_is_bit_exact(c):
     """every case of the GPU file: the exactness conditions hold on the float64 reference (forward-only launch and forward +
-    backward), the mask has what the family promises, and the fp32 emulation of the kernels - version 2, and version 1 for
-    the child's cases - equals the reference rounded once, bit for bit (lse within LSE_ULPS; the worst seen is printed)"""
+    backward), the mask has what the family promises, and the fp32 emulation of the kernels
+    equals the reference rounded once, bit for bit (lse within LSE_ULPS; the worst seen is printed)"""
     ops = R.make_operands(c)
     keep = R.random_keep(c) if c.family == "dropout" else None
     if c.live is not None:
@@ -110,14 +110,13 @@ def test_conditions_hold_and_emulation_is_bit_exact(c):
     for fwd in (True, False):
         ref = R.reference_of(c, ops, keep, forward_only=fwd)
         R.assert_exact_conditions(c, ops, ref, forward_only=fwd)
-        for ver in ((1,) if c.name.startswith("v1") else (2,)):
-            emu = R.emulation_of(c, ops, keep, forward_only=fwd, version=ver)
-            assert R.exact_mismatches(emu, ref, forward_only=fwd) == [], (c, fwd, ver)
-            fin = torch.isfinite(ref.lse) & (ref.lse != 0)
-            if bool(fin.any()):
-                u = float(((emu.lse.double() - ref.lse).abs() / R.ulp32(ref.lse))[fin].max())
-                print("lse ulps", c.name, u)
-                assert u <= 1.0
+        emu = R.emulation_of(c, ops, keep, forward_only=fwd)
+        assert R.exact_mismatches(emu, ref, forward_only=fwd) == [], (c, fwd)
+        fin = torch.isfinite(ref.lse) & (ref.lse != 0)
+        if bool(fin.any()):
+            u = float(((emu.lse.double() - ref.lse).abs() / R.ulp32(ref.lse))[fin].max())
+            print("lse ulps", c.name, u)
+            assert u <= 1.0
     if c.family == "gather" and c.Lk > 256 and c.live and c.live[0]:
         S = ref.S[0]
         cm = torch.stack([S[..., a:a + 128].amax(-1) for a in range(0, c.Lk, 128)], -1).cummax(-1).values
@@ -133,8 +132,7 @@ def test_mutants_fail_exactly_and_pass_the_norm(c):
     it as the reference: the error a norm cannot see"""
     ops = R.make_operands(c)
     keep = R.random_keep(c) if c.family == "dropout" else None
-    ver = 1 if c.name.startswith("v1") else 2
-    R.check_mutants(c, ops, keep, lambda fwd: R.emulation_of(c, ops, keep, forward_only=fwd, version=ver))
+    R.check_mutants(c, ops, keep, lambda fwd: R.emulation_of(c, ops, keep, forward_only=fwd))
 
 
 def _numerics(nc):
@@ -149,7 +147,7 @@ def test_emulation_stays_inside_the_derived_bounds(nc):
     delta, dq, dk, dv within mha_ref.error_bounds (ratios 0.01 .. 0.98).  With u = 2^-9 in place of bf16's unit roundoff 2^-8
     the emulation exceeds them (O 2.0, dv 1.3 on the peaked case): the rounding of one bf16 number alone reaches 2^-8."""
     ops, ref, bounds = _numerics(nc)
-    emu = R.emulate_kernel(ops.q, ops.k, ops.v, ops.dout, ops.mask, R.NSCALE, nc.H, o32=nc.o32, version=2)
+    emu = R.emulate_kernel(ops.q, ops.k, ops.v, ops.dout, ops.mask, R.NSCALE, nc.H, o32=nc.o32)
     rat = R.bound_ratios(emu, ref, bounds)
     print(nc.name, {k: "%.2f (median bound/|value| %.1e)" % v for k, v in rat.items()})
     assert all(v[0] <= 1.0 for v in rat.values()), rat

@@ -28,6 +28,7 @@
 #include <string.h>
 #include <vector>
 #include "common.h"
+#include "mfma_tile.h"   // tr_read2
 
 struct Wg2K {
   const __bf16* x;
@@ -46,18 +47,6 @@ struct Wg2K {
 };
 
 __device__ uint4 g_mi_zero_page[4];
-
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-__device__ __forceinline__ bf16x8 tr_read2(const char* base0, const char* base1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base1));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 // 16-byte LDS-DMA: LDS[lds_off + lane*16 .. +16) = *g   (lds_off wave-uniform).  Issued from inline asm so the
 // compiler neither tracks it on vmcnt nor fences later ds_reads with vmcnt(0): the loop below waits explicitly.

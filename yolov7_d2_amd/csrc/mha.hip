@@ -20,23 +20,13 @@
 //                   O / dQ += P (A: [16 q][32 key slots]) x V / K (B via ds_read_b64_tr_b16 from row-major LDS).
 //   dK, dV      :  S tile = Q_tile (A) x K^T (B) -> lane (t = key, g) holds queries 4g..4g+3, again directly the
 //                   A fragment of dV += P^T dO and dK += dS^T Q.
-// A wave owns 16 queries (forward, dQ) or 16 keys (dK/dV); a block = 4 waves shares the K/V (or Q/dO) tiles in LDS.
-#include <stdlib.h>
+// A wave owns 16 queries (forward, dQ) or 16 keys (dK/dV); a block = 4 .. 12 waves (mha2_waves: one round of blocks on the
+// device) shares the K/V (or Q/dO) chunks of 128 rows in LDS.  The LDS tile and its fragment reads are mfma_tile.h's.
 #include <string.h>
 #include "common.h"
+#include "mfma_tile.h"
 
 #define MHA_D 32
-
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr_;
-__device__ __forceinline__ bf16x8 mha_tr_read2(const char* base0, const char* base1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr_)(base0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr_)(base1));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 struct MhaK {
   const __bf16* q;
@@ -78,137 +68,9 @@ __device__ __forceinline__ float mha_keep(const MhaK& p, unsigned long long rk, 
   return mi_rng32k(rk, base + off) >= p.drop_thr ? p.drop_scale : 0.f;
 }
 
-// LDS tile of 32 rows x 32 d (64-byte rows), 16-byte chunks XOR-swizzled by (row >> 2) & 3 for the direct b128
-// fragment reads and -- equivalently for 32-byte groups -- (row >> 2) & 1 for the transpose reads.
-__device__ __forceinline__ int tile_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-// stage rows [r0, r0+32) of a [L][B][E] tensor (head h, batch b) into a tile; rows >= L are zero
-__device__ __forceinline__ void stage_tile(char* T, const __bf16* src, int r0, int L, int B, int E, int b, int h,
-                                           int tid) {
-  if (tid >= 0 && tid < 128) {
-    const int row = tid >> 2, chunk = tid & 3;
-    u32x4 val = {0u, 0u, 0u, 0u};
-    if (r0 + row < L) val = *(const u32x4*)(src + ((size_t)(r0 + row) * B + b) * E + h * MHA_D + chunk * 8);
-    *(u32x4*)(T + tile_off(row, chunk)) = val;
-  }
-}
-
-// direct fragment: lane (t = row, g) -> 8 consecutive d = 8g..8g+7 of row (r16*16 + t)
-__device__ __forceinline__ bf16x8 frag_rows(const char* T, int r16, int t, int g) {
-  return __builtin_bit_cast(bf16x8, *(const u32x4*)(T + tile_off(r16 * 16 + t, g)));
-}
-// transposed fragment for the B operand "rows as k slots": lane (t = d within group j, g) -> rows 4g+{0..3} and
-// 16+4g+{0..3}; d group j in {0,1}
-__device__ __forceinline__ bf16x8 frag_cols(const char* T, int j, int t, int g) {
-  const int r0 = 4 * g + (t >> 2), r1 = 16 + r0;
-  // 32-byte group j of a row sits at chunks 2j, 2j+1 -> swizzled by the same XOR (it preserves the pair: the XOR
-  // value's low bit moves within the pair only if odd, so build the address per 8-byte piece explicitly)
-  const int piece = t & 3;                    // 8-byte piece inside the 32-byte group
-  const int c0 = 2 * j + (piece >> 1);        // 16-byte chunk holding the piece
-  const int a0 = tile_off(r0, c0) + (piece & 1) * 8;
-  const int a1 = tile_off(r1, c0) + (piece & 1) * 8;
-  return mha_tr_read2(T + a0, T + a1);
-}
-
-// ------------------------------------------------------------------ forward
-__global__ __launch_bounds__(256) void mha_fwd_kernel(const MhaK p) {
-  const unsigned long long rk = mha_rng_key(p);
-  __shared__ __attribute__((aligned(16))) char Ks[2][2048], Vs[2][2048];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = lane & 15, g = lane >> 4;
-  const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
-  const int q0 = blockIdx.x * 64 + wave * 16;
-  // this lane's query (B operand of S^T: lane (t = query, g) holds d = 8g..8g+7)
-  bf16x8 qf = {};
-  const int myq = q0 + t;
-  if (myq < p.Lq) qf = *(const bf16x8*)(p.q + ((size_t)myq * p.B + b) * p.ldq + h * MHA_D + g * 8);
-  f32x4 oacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // [d group]: lane (t = d, g): queries 4g+r
-  float m_run = -INFINITY, l_run = 0.f;  // of query `t` (replicated over g)
-  const int ntiles = (p.Lk + 31) / 32;
-  stage_tile(Ks[0], p.k, 0, p.Lk, p.B, p.ldk, b, h, tid);
-  stage_tile(Vs[0], p.v, 0, p.Lk, p.B, p.E, b, h, tid - 128);
-  for (int it = 0; it < ntiles; ++it) {
-    __syncthreads();
-    const int cur = it & 1;
-    if (it + 1 < ntiles) {
-      stage_tile(Ks[cur ^ 1], p.k, (it + 1) * 32, p.Lk, p.B, p.ldk, b, h, tid);
-      stage_tile(Vs[cur ^ 1], p.v, (it + 1) * 32, p.Lk, p.B, p.E, b, h, tid - 128);
-    }
-    const int k0 = it * 32;
-    // S^T tiles: keys [0,16) and [16,32) of this tile x 16 queries
-    f32x4 s[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const bf16x8 kf = frag_rows(Ks[cur], a, t, g);
-      s[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    }
-    // lane (t = query, g): s[a][r] = score of key k0 + 16a + 4g + r
-    float sv[8];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = k0 + 16 * a + 4 * g + r;
-        float x = s[a][r] * p.scale;
-        const bool dead = key >= p.Lk || (p.mask && p.mask[(size_t)b * p.Lk + key]);
-        x = dead ? -INFINITY : x;
-        sv[a * 4 + r] = x;
-        mx = fmaxf(mx, x);
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = (m_new == -INFINITY) ? 1.f : __expf(m_run - m_new);  // (m_run = -inf -> 0)
-    float psum = 0.f;
-    bf16x8 pf;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float pe = (m_new == -INFINITY) ? 0.f : __expf(sv[e] - m_new);
-      psum += pe;           // the softmax normaliser is taken BEFORE the dropout, as F.multi_head_attention_forward does
-      pf[e] = (__bf16)(pe * mha_keep(p, rk, b, h, myq, k0 + 16 * (e >> 2) + 4 * g + (e & 3)));
-    }
-    psum += __shfl_xor(psum, 16, 64);
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-    // rescale O: lane (t = d, g) holds queries 4g + r -> alpha of lane (4g + r)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float ar = __shfl(alpha, 4 * g + r, 64);
-      oacc[0][r] *= ar;
-      oacc[1][r] *= ar;
-    }
-    // O += P (A: lane (t = query, g), 8 key slots) x V (B: transpose read, d group j)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const bf16x8 vf = frag_cols(Vs[cur], j, t, g);
-      oacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, oacc[j], 0, 0, 0);
-    }
-  }
-  // epilogue: O[q][d] / l ; lane (t = d, g): queries 4g + r
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int qq = q0 + 4 * g + r;
-    const float lr = __shfl(l_run, 4 * g + r, 64);
-    const float inv = lr > 0.f ? 1.f / lr : 0.f;
-    if (qq < p.Lq) {
-      __bf16* op = p.o + ((size_t)qq * p.B + b) * p.E + h * MHA_D;
-      op[t] = (__bf16)(oacc[0][r] * inv);
-      op[16 + t] = (__bf16)(oacc[1][r] * inv);
-      if (p.o32) {
-        float* o3 = p.o32 + ((size_t)qq * p.B + b) * p.E + h * MHA_D;
-        o3[t] = oacc[0][r] * inv;
-        o3[16 + t] = oacc[1][r] * inv;
-      }
-    }
-  }
-  if (g == 0 && myq < p.Lq && p.lse)
-    p.lse[((size_t)b * p.H + h) * p.Lq + myq] = (l_run > 0.f) ? m_run + __logf(l_run) : -INFINITY;
-}
-
 // ------------------------------------------------------------------ forward, version 2
-// The first kernel crossed a block barrier and staged 2 + 2 KB for every 32 keys (33 barriers at L = 1050), gave each wave
+// The first kernel (deleted; priced against this one in profiles/mha_v1_removal_ab.txt) crossed a block barrier
+// and staged 2 + 2 KB for every 32 keys (33 barriers at L = 1050), gave each wave
 // 16 queries of a 64-query block (544 blocks of 4 waves) and ran one softmax update - two cross-lane maxima, two sums, four
 // broadcasts of the rescale factor - per 4 tiny MFMAs: 92 TFLOP/s kernel-only at B = 4, L = 1050.  With head_dim 32 the
 // matrix cores are NOT the limit (128 flops per score = 0.13 SIMD cycles): the kernel is bound by vector instructions per
@@ -228,6 +90,40 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const MhaK p) {
 // (Measured and dropped: sharing a 16-query group between four waves by chunk to even out the SIMDs - the waves run in
 // lockstep with the chunk barriers, so the split group is still processed serially.)
 #define MHA2_KC 128
+
+// This thread's share of a chunk of MHA2_KC rows of the two streamed operands (K and V, or Q and dO), head h of batch b: two
+// 16-byte pieces of each (512 pieces per operand; a block of more than 256 threads repeats the last piece).  Loads are
+// unconditional - rows past the last one repeat it (finite values; the kernel gives them a bias of -inf, a weight of exactly
+// 0) - so that nothing but the LDS store waits for them.  LDS: per buffer four 32-row tiles (mfma_tile.h) per operand.
+struct MhaChunk {
+  u32x4 areg[2], breg[2];
+  __device__ __forceinline__ void load(const __bf16* A, int lda, const __bf16* B, int ldb, int r0, int L, int nb, int b, int h,
+                                       int tid, int nth) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      int idx = tid + u * nth;
+      idx = idx < 511 ? idx : 511;
+      int row = r0 + (idx >> 2);
+      row = row < L ? row : L - 1;
+      const size_t rb = (size_t)row * nb + b;
+      const int tail = h * MHA_D + (idx & 3) * 8;
+      areg[u] = *(const u32x4*)(A + rb * lda + tail);
+      breg[u] = *(const u32x4*)(B + rb * ldb + tail);
+    }
+  }
+  __device__ __forceinline__ void store(char* As, char* Bs, int buf, int tid, int nth) const {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      int idx = tid + u * nth;
+      idx = idx < 511 ? idx : 511;
+      const int row = idx >> 2;
+      const int o = buf * 8192 + (row >> 5) * 2048 + tile_off(row & 31, idx & 3);
+      *(u32x4*)(As + o) = areg[u];
+      *(u32x4*)(Bs + o) = breg[u];
+    }
+  }
+};
+
 template <bool DROP>
 __global__ __launch_bounds__(768) void mha_fwd2_kernel(const MhaK p) {
   const unsigned long long rk = mha_rng_key(p);
@@ -249,39 +145,19 @@ __global__ __launch_bounds__(768) void mha_fwd2_kernel(const MhaK p) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.f;
   const int nchunks = (p.Lk + MHA2_KC - 1) / MHA2_KC;
-  // this thread's share of a chunk: two 16-byte pieces of K and of V (512 pieces each; a block of more than 256 threads
-  // repeats the last piece) and one mask byte.  Loads are unconditional - rows past the last key repeat it (finite
-  // values; their bias is -inf, their weight exactly 0) - so that nothing but the LDS store waits for them.
-  u32x4 kreg[2], vreg[2];
+  // this thread's share of a chunk: its pieces of K and V and one mask byte (loaded unconditionally, as the pieces are)
+  MhaChunk kv;
   unsigned char mreg = 0;
   const uint8_t* const mrow = p.mask ? p.mask + (size_t)b * p.Lk : (const uint8_t*)p.k;
   auto load_chunk = [&](int c) {
     const int k0 = c * MHA2_KC;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int idx = tid + u * nth;
-      idx = idx < 511 ? idx : 511;
-      int row = k0 + (idx >> 2);
-      row = row < p.Lk ? row : p.Lk - 1;
-      const size_t rb = (size_t)row * p.B + b;
-      const int tail = h * MHA_D + (idx & 3) * 8;
-      kreg[u] = *(const u32x4*)(p.k + rb * p.ldk + tail);
-      vreg[u] = *(const u32x4*)(p.v + rb * p.E + tail);
-    }
+    kv.load(p.k, p.ldk, p.v, p.E, k0, p.Lk, p.B, b, h, tid, nth);
     const int key = k0 + (tid & (MHA2_KC - 1));
     mreg = mrow[key < p.Lk ? key : p.Lk - 1];
   };
   auto store_chunk = [&](int c) {
     const int buf = c & 1;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int idx = tid + u * nth;
-      idx = idx < 511 ? idx : 511;
-      const int row = idx >> 2;
-      const int o = buf * 8192 + (row >> 5) * 2048 + tile_off(row & 31, idx & 3);
-      *(u32x4*)(Ks + o) = kreg[u];
-      *(u32x4*)(Vs + o) = vreg[u];
-    }
+    kv.store(Ks, Vs, buf, tid, nth);
     const int key = c * MHA2_KC + (tid & (MHA2_KC - 1));
     Mb[buf][tid & (MHA2_KC - 1)] = (key >= p.Lk || (p.mask && mreg)) ? -INFINITY : 0.f;
   };
@@ -407,145 +283,6 @@ __global__ __launch_bounds__(256) void mha_delta_kernel(const MhaK p, float* del
   if (part == 0) delta[row] = s;
 }
 
-// dQ: same loop structure as the forward (a wave owns 16 queries, streams K/V tiles)
-__global__ __launch_bounds__(256) void mha_bwd_dq_kernel(const MhaK p) {
-  const unsigned long long rk = mha_rng_key(p);
-  __shared__ __attribute__((aligned(16))) char Ks[2][2048], Vs[2][2048];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = lane & 15, g = lane >> 4;
-  const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
-  const int q0 = blockIdx.x * 64 + wave * 16;
-  const int myq = q0 + t;
-  bf16x8 qf = {}, dof = {};
-  float lse = 0.f, dl = 0.f;
-  if (myq < p.Lq) {
-    const size_t rb = (size_t)myq * p.B + b;
-    qf = *(const bf16x8*)(p.q + rb * p.ldq + h * MHA_D + g * 8);
-    dof = *(const bf16x8*)(p.dout + rb * p.E + h * MHA_D + g * 8);
-    lse = p.lse[((size_t)b * p.H + h) * p.Lq + myq];
-    dl = p.delta[((size_t)b * p.H + h) * p.Lq + myq];
-  }
-  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  const int ntiles = (p.Lk + 31) / 32;
-  stage_tile(Ks[0], p.k, 0, p.Lk, p.B, p.ldk, b, h, tid);
-  stage_tile(Vs[0], p.v, 0, p.Lk, p.B, p.E, b, h, tid - 128);
-  for (int it = 0; it < ntiles; ++it) {
-    __syncthreads();
-    const int cur = it & 1;
-    if (it + 1 < ntiles) {
-      stage_tile(Ks[cur ^ 1], p.k, (it + 1) * 32, p.Lk, p.B, p.ldk, b, h, tid);
-      stage_tile(Vs[cur ^ 1], p.v, (it + 1) * 32, p.Lk, p.B, p.E, b, h, tid - 128);
-    }
-    const int k0 = it * 32;
-    bf16x8 dsf;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const bf16x8 kf = frag_rows(Ks[cur], a, t, g), vf = frag_rows(Vs[cur], a, t, g);
-      const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = k0 + 16 * a + 4 * g + r;
-        const bool dead = key >= p.Lk || (p.mask && p.mask[(size_t)b * p.Lk + key]) || myq >= p.Lq;
-        const float pe = (dead || lse == -INFINITY) ? 0.f : __expf(s[r] * p.scale - lse);
-        dsf[a * 4 + r] = (__bf16)(pe * (dp[r] * mha_keep(p, rk, b, h, myq, key) - dl) * p.scale);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const bf16x8 kc = frag_cols(Ks[cur], j, t, g);
-      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf, kc, acc[j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int qq = q0 + 4 * g + r;
-    if (qq < p.Lq) {
-      __bf16* op = p.dq + ((size_t)qq * p.B + b) * p.ldq + h * MHA_D;
-      op[t] = (__bf16)acc[0][r];
-      op[16 + t] = (__bf16)acc[1][r];
-    }
-  }
-}
-
-// dK, dV: a wave owns 16 keys and streams Q / dO tiles
-__global__ __launch_bounds__(256) void mha_bwd_dkv_kernel(const MhaK p) {
-  const unsigned long long rk = mha_rng_key(p);
-  __shared__ __attribute__((aligned(16))) char Qs[2][2048], Ds[2][2048];
-  __shared__ float Ls[2][32], Dl[2][32];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = lane & 15, g = lane >> 4;
-  const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
-  const int key0 = blockIdx.x * 64 + wave * 16;
-  const int mykey = key0 + t;
-  bf16x8 kf = {}, vf = {};
-  bool kdead = mykey >= p.Lk;
-  if (!kdead) {
-    const size_t rb = (size_t)mykey * p.B + b;
-    kf = *(const bf16x8*)(p.k + rb * p.ldk + h * MHA_D + g * 8);
-    vf = *(const bf16x8*)(p.v + rb * p.E + h * MHA_D + g * 8);
-    kdead = p.mask && p.mask[(size_t)b * p.Lk + mykey];
-  }
-  f32x4 dk[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  f32x4 dv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  const int ntiles = (p.Lq + 31) / 32;
-  auto stage_stats = [&](int buf, int r0) {
-    if (tid >= 192 && tid < 224) {
-      const int row = tid - 192;
-      const bool ok = r0 + row < p.Lq;
-      float lv = ok ? p.lse[((size_t)b * p.H + h) * p.Lq + r0 + row] : INFINITY;  // exp(s - inf) = 0
-      if (lv == -INFINITY) lv = INFINITY;  // fully masked query row: contributes nothing
-      Ls[buf][row] = lv;
-      Dl[buf][row] = ok ? p.delta[((size_t)b * p.H + h) * p.Lq + r0 + row] : 0.f;
-    }
-  };
-  stage_tile(Qs[0], p.q, 0, p.Lq, p.B, p.ldq, b, h, tid);
-  stage_tile(Ds[0], p.dout, 0, p.Lq, p.B, p.E, b, h, tid - 128);
-  stage_stats(0, 0);
-  for (int it = 0; it < ntiles; ++it) {
-    __syncthreads();
-    const int cur = it & 1;
-    if (it + 1 < ntiles) {
-      stage_tile(Qs[cur ^ 1], p.q, (it + 1) * 32, p.Lq, p.B, p.ldq, b, h, tid);
-      stage_tile(Ds[cur ^ 1], p.dout, (it + 1) * 32, p.Lq, p.B, p.E, b, h, tid - 128);
-      stage_stats(cur ^ 1, (it + 1) * 32);
-    }
-    bf16x8 pf, dsf;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      // S tile = Q (A: lane (t = query 16a + t, g)) x K^T (B: lane (t = key, g)) -> lane (t = key, g): queries 16a+4g+r
-      const bf16x8 qa = frag_rows(Qs[cur], a, t, g), da = frag_rows(Ds[cur], a, t, g);
-      const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int ql = 16 * a + 4 * g + r;
-        const float pe = kdead ? 0.f : __expf(s[r] * p.scale - Ls[cur][ql]);
-        const float keep = mha_keep(p, rk, b, h, it * 32 + ql, mykey);
-        pf[a * 4 + r] = (__bf16)(pe * keep);
-        dsf[a * 4 + r] = (__bf16)(pe * (dp[r] * keep - Dl[cur][ql]) * p.scale);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const bf16x8 dc = frag_cols(Ds[cur], j, t, g), qc = frag_cols(Qs[cur], j, t, g);
-      dv[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, dc, dv[j], 0, 0, 0);
-      dk[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf, qc, dk[j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int kk = key0 + 4 * g + r;
-    if (kk < p.Lk) {
-      const size_t off = ((size_t)kk * p.B + b) * p.E + h * MHA_D, offk = ((size_t)kk * p.B + b) * p.ldk + h * MHA_D;
-      p.dk[offk + t] = (__bf16)dk[0][r];
-      p.dk[offk + 16 + t] = (__bf16)dk[1][r];
-      p.dv[off + t] = (__bf16)dv[0][r];
-      p.dv[off + 16 + t] = (__bf16)dv[1][r];
-    }
-  }
-}
-
 // ------------------------------------------------------------------ backward, version 2
 // The forward v2 structure for the two backward kernels: nwv waves x 16 rows per block sized to one round of blocks, the
 // streamed operand pair in 128-row LDS chunks (double-buffered, one barrier per chunk, unconditional prefetch loads), one
@@ -578,36 +315,18 @@ __global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const MhaK p) {
   f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   const f32x4 ndl = DROP ? f32x4{0.f, 0.f, 0.f, 0.f} : f32x4{-dl, -dl, -dl, -dl};
   const int nchunks = (p.Lk + MHA2_KC - 1) / MHA2_KC;
-  u32x4 kreg[2], vreg[2];
+  MhaChunk kv;
   unsigned char mreg = 0;
   const uint8_t* const mrow = p.mask ? p.mask + (size_t)b * p.Lk : (const uint8_t*)p.k;
   auto load_chunk = [&](int c) {
     const int k0 = c * MHA2_KC;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int idx = tid + u * nth;
-      idx = idx < 511 ? idx : 511;
-      int row = k0 + (idx >> 2);
-      row = row < p.Lk ? row : p.Lk - 1;
-      const size_t rb = (size_t)row * p.B + b;
-      const int tail = h * MHA_D + (idx & 3) * 8;
-      kreg[u] = *(const u32x4*)(p.k + rb * p.ldk + tail);
-      vreg[u] = *(const u32x4*)(p.v + rb * p.E + tail);
-    }
+    kv.load(p.k, p.ldk, p.v, p.E, k0, p.Lk, p.B, b, h, tid, nth);
     const int key = k0 + (tid & (MHA2_KC - 1));
     mreg = mrow[key < p.Lk ? key : p.Lk - 1];
   };
   auto store_chunk = [&](int c) {
     const int buf = c & 1;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int idx = tid + u * nth;
-      idx = idx < 511 ? idx : 511;
-      const int row = idx >> 2;
-      const int o = buf * 8192 + (row >> 5) * 2048 + tile_off(row & 31, idx & 3);
-      *(u32x4*)(Ks + o) = kreg[u];
-      *(u32x4*)(Vs + o) = vreg[u];
-    }
+    kv.store(Ks, Vs, buf, tid, nth);
     const int key = c * MHA2_KC + (tid & (MHA2_KC - 1));
     Mb[buf][tid & (MHA2_KC - 1)] = (key >= p.Lk || (p.mask && mreg)) ? -INFINITY : 0.f;
   };
@@ -681,38 +400,20 @@ __global__ __launch_bounds__(768) void mha_bwd_dkv2_kernel(const MhaK p) {
   f32x4 dk[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   f32x4 dv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   const int nchunks = (p.Lq + MHA2_KC - 1) / MHA2_KC;
-  u32x4 qreg[2], dreg[2];
+  MhaChunk qd;
   float lreg = 0.f, ereg = 0.f;
   const float* const lrow = p.lse + ((size_t)b * p.H + h) * p.Lq;
   const float* const drow = p.delta + ((size_t)b * p.H + h) * p.Lq;
   auto load_chunk = [&](int c) {
     const int r0 = c * MHA2_KC;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int idx = tid + u * nth;
-      idx = idx < 511 ? idx : 511;
-      int row = r0 + (idx >> 2);
-      row = row < p.Lq ? row : p.Lq - 1;
-      const size_t rb = (size_t)row * p.B + b;
-      const int tail = h * MHA_D + (idx & 3) * 8;
-      qreg[u] = *(const u32x4*)(p.q + rb * p.ldq + tail);
-      dreg[u] = *(const u32x4*)(p.dout + rb * p.E + tail);
-    }
+    qd.load(p.q, p.ldq, p.dout, p.E, r0, p.Lq, p.B, b, h, tid, nth);
     const int qq = r0 + (tid & (MHA2_KC - 1));
     lreg = lrow[qq < p.Lq ? qq : p.Lq - 1];
     ereg = drow[qq < p.Lq ? qq : p.Lq - 1];
   };
   auto store_chunk = [&](int c) {
     const int buf = c & 1;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      int idx = tid + u * nth;
-      idx = idx < 511 ? idx : 511;
-      const int row = idx >> 2;
-      const int o = buf * 8192 + (row >> 5) * 2048 + tile_off(row & 31, idx & 3);
-      *(u32x4*)(Qs + o) = qreg[u];
-      *(u32x4*)(Ds + o) = dreg[u];
-    }
+    qd.store(Qs, Ds, buf, tid, nth);
     const int qq = c * MHA2_KC + (tid & (MHA2_KC - 1));
     const bool live = qq < p.Lq && lreg != -INFINITY;   // (a fully masked query row contributes nothing)
     Nl[buf][tid & (MHA2_KC - 1)] = live ? -lreg * 1.44269504088896341f : -INFINITY;
@@ -854,12 +555,6 @@ extern "C" int mi_mha_fwd_dropout_ld(const void* q, int ldq, const void* k, int 
   p.o = (__bf16*)o; p.o32 = o_f32; p.lse = lse; p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.E = E; p.scale = scale;
   p.ldq = ldq; p.ldk = ldk;
   MI_REQUIRE(!o_f32 || ((uintptr_t)o_f32 & 15) == 0, "mha_fwd: o_f32 alignment");
-  static const int v2 = getenv("MI_MHA_V2") ? atoi(getenv("MI_MHA_V2")) : 1;
-  if (!v2) {
-    hipLaunchKernelGGL(mha_fwd_kernel, dim3(mi_cdiv(Lq, 64), B * H), dim3(256), 0, (hipStream_t)st, p);
-    MI_CHECK_LAUNCH("mha_fwd");
-    return MI_OK;
-  }
   const int nwv = mha2_waves(Lq, B * H);
   const dim3 grid(mi_cdiv(mi_cdiv(Lq, 16), nwv), B * H), blk(nwv * 64);
   if (p.drop_thr) hipLaunchKernelGGL(mha_fwd2_kernel<true>, grid, blk, 0, (hipStream_t)st, p);
@@ -931,14 +626,6 @@ extern "C" int mi_mha_bwd_dropout_ld(const void* q, int ldq, const void* k, int 
   hipStream_t s = (hipStream_t)st;
   hipLaunchKernelGGL(mha_delta_kernel, dim3(mi_cdiv(B * H * Lq * 4, 256)), dim3(256), 0, s, p, delta_ws);
   MI_CHECK_LAUNCH("mha_delta");
-  static const int v2 = getenv("MI_MHA_V2") ? atoi(getenv("MI_MHA_V2")) : 1;
-  if (!v2) {
-    hipLaunchKernelGGL(mha_bwd_dq_kernel, dim3(mi_cdiv(Lq, 64), B * H), dim3(256), 0, s, p);
-    MI_CHECK_LAUNCH("mha_bwd_dq");
-    hipLaunchKernelGGL(mha_bwd_dkv_kernel, dim3(mi_cdiv(Lk, 64), B * H), dim3(256), 0, s, p);
-    MI_CHECK_LAUNCH("mha_bwd_dkv");
-    return MI_OK;
-  }
   const int nq = mha2_waves(Lq, B * H), nk = mha2_waves(Lk, B * H);
   const dim3 gq(mi_cdiv(mi_cdiv(Lq, 16), nq), B * H), gk(mi_cdiv(mi_cdiv(Lk, 16), nk), B * H);
   if (p.drop_thr) hipLaunchKernelGGL(mha_bwd_dq2_kernel<true>, gq, dim3(nq * 64), 0, s, p);

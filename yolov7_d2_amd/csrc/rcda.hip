@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
+#include "mfma_tile.h"   // tile_off, frag_rows, frag_cols: the LDS tile and fragment layouts shared with mha.hip
 
 #define RC_D 32
 #define RC_MAX 96              // served map side: H, W <= 96 (a dilated C5 map at 800 x 1333 is 50 x 84)
@@ -35,28 +36,6 @@
 
 typedef mi_rcda_desc RcK;
 
-typedef __attribute__((address_space(3))) s16x4* rc_lds_s16x4_ptr;
-__device__ __forceinline__ bf16x8 rc_tr_read2(const char* base0, const char* base1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rc_lds_s16x4_ptr)(base0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rc_lds_s16x4_ptr)(base1));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-// LDS tile of 32 rows x 32 d (64-byte rows), 16-byte chunks XOR-swizzled by (row >> 2) & 3 (the tile of mha.hip)
-__device__ __forceinline__ int rc_tile_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-// direct fragment: lane (t = row, g) -> d = 8g..8g+7 of row r16 * 16 + t
-__device__ __forceinline__ bf16x8 rc_frag_rows(const char* T, int r16, int t, int g) {
-  return __builtin_bit_cast(bf16x8, *(const u32x4*)(T + rc_tile_off(r16 * 16 + t, g)));
-}
-// transposed fragment "rows as k slots": lane (t = d within group j, g) -> rows 4g+{0..3} and 16+4g+{0..3}
-__device__ __forceinline__ bf16x8 rc_frag_cols(const char* T, int j, int t, int g) {
-  const int r0 = 4 * g + (t >> 2), r1 = 16 + r0;
-  const int piece = t & 3, c0 = 2 * j + (piece >> 1);
-  return rc_tr_read2(T + rc_tile_off(r0, c0) + (piece & 1) * 8, T + rc_tile_off(r1, c0) + (piece & 1) * 8);
-}
 __device__ __forceinline__ f32x4 rc_mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float rc_sum_g(float v) {   // sum over the four lane groups g of a query / key t, in a fixed order
   v += __shfl_xor(v, 16, 64);
@@ -138,7 +117,7 @@ struct RcVStage {
       const int row = idx >> 2, piece = idx & 3;
       hh[u] = row / WP;
       const int w = row - hh[u] * WP;
-      off[u] = (row >> 5) * 2048 + rc_tile_off(row & 31, piece);
+      off[u] = (row >> 5) * 2048 + tile_off(row & 31, piece);
       src[u] = vb + (size_t)(w < W ? w : W - 1) * ldv + piece * 8;
     }
   }
@@ -243,7 +222,7 @@ __global__ __launch_bounds__(256) void rc_fwd_kernel(const RcK p) {
           for (int e = 0; e < 8; ++e) pf[e] = (__bf16)(ah * arow[2 * t2 + (e >> 2)][e & 3]);
           const char* T = V + (hh * nW32 + t2) * 2048;
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc[j] = rc_mfma(pf, rc_frag_cols(T, j, t, g), acc[j]);
+          for (int j = 0; j < 2; ++j) acc[j] = rc_mfma(pf, frag_cols(T, j, t, g), acc[j]);
         }
       }
     }
@@ -287,7 +266,7 @@ __global__ __launch_bounds__(256) void rc_bwd_q_kernel(const RcK p, __bf16* wsr,
     u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
     if (row < p.W) a = *(const u32x4*)(krb + (size_t)row * p.ldk + piece * 8);
     if (row < p.H) c = *(const u32x4*)(kcb + (size_t)row * p.ldk + piece * 8);
-    const int o = (row >> 5) * 2048 + rc_tile_off(row & 31, piece);
+    const int o = (row >> 5) * 2048 + tile_off(row & 31, piece);
     *(u32x4*)(Krs + o) = a;
     *(u32x4*)(Kcs + o) = c;
   }
@@ -326,7 +305,7 @@ __global__ __launch_bounds__(256) void rc_bwd_q_kernel(const RcK p, __bf16* wsr,
       for (int i = 0; i < RC_NT; ++i) {
         if (i < nWt) {
           // T^T tile: V[h] rows (A: 16 columns w x 32 d) x dO^T (B) -> lane (t = query, g): w = 16 i + 4 g + r
-          const f32x4 T = rc_mfma(rc_frag_rows(V + (hh * nW32 + (i >> 1)) * 2048, i & 1, t, g), dof, f32x4{0.f, 0.f, 0.f, 0.f});
+          const f32x4 T = rc_mfma(frag_rows(V + (hh * nW32 + (i >> 1)) * 2048, i & 1, t, g), dof, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             dar[i][r] += ah * T[r];
@@ -378,11 +357,11 @@ __global__ __launch_bounds__(256) void rc_bwd_q_kernel(const RcK p, __bf16* wsr,
     }
     if (t2 < nW32) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) ar[j] = rc_mfma(fr, rc_frag_cols(Krs + t2 * 2048, j, t, g), ar[j]);
+      for (int j = 0; j < 2; ++j) ar[j] = rc_mfma(fr, frag_cols(Krs + t2 * 2048, j, t, g), ar[j]);
     }
     if (t2 < nH32) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) ac[j] = rc_mfma(fc, rc_frag_cols(Kcs + t2 * 2048, j, t, g), ac[j]);
+      for (int j = 0; j < 2; ++j) ac[j] = rc_mfma(fc, frag_cols(Kcs + t2 * 2048, j, t, g), ac[j]);
     }
   }
 #pragma unroll
@@ -488,7 +467,7 @@ __global__ __launch_bounds__(512) void rc_bwd_v_kernel(const RcK p) {
     }
   };
   auto store = [&]() {
-    if (which < 3) *(u32x4*)((which == 0 ? Qr : which == 1 ? Qc : Do) + rc_tile_off(row, piece)) = reg;
+    if (which < 3) *(u32x4*)((which == 0 ? Qr : which == 1 ? Qc : Do) + tile_off(row, piece)) = reg;
     else if (tid < 448) ((tid & 32) ? Lc : Lr)[tid & 31] = lreg == -INFINITY ? INFINITY : lreg;   // (a dead query weighs nothing)
   };
   const int nsteps = (p.L + 31) >> 5;
@@ -502,7 +481,7 @@ __global__ __launch_bounds__(512) void rc_bwd_v_kernel(const RcK p) {
       // A_col^T: Qc tile rows (A: 16 queries) x Kc^T (B: lane (t = h, g)) -> lane (t = h, g): queries 16 a + 4 g + r
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
-        const f32x4 s = rc_mfma(rc_frag_rows(Qc, a, t, g), kcf, f32x4{0.f, 0.f, 0.f, 0.f});
+        const f32x4 s = rc_mfma(frag_rows(Qc, a, t, g), kcf, f32x4{0.f, 0.f, 0.f, 0.f});
         const f32x4 lr4 = *(const f32x4*)(&Lr[16 * a + 4 * g]), lc4 = *(const f32x4*)(&Lc[16 * a + 4 * g]);
         f32x4 o;
 #pragma unroll
@@ -514,12 +493,12 @@ __global__ __launch_bounds__(512) void rc_bwd_v_kernel(const RcK p) {
     float ar[8];
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-      const f32x4 s = rc_mfma(rc_frag_rows(Qr, a, t, g), krf, f32x4{0.f, 0.f, 0.f, 0.f});
+      const f32x4 s = rc_mfma(frag_rows(Qr, a, t, g), krf, f32x4{0.f, 0.f, 0.f, 0.f});
       const f32x4 lr4 = *(const f32x4*)(&Lr[16 * a + 4 * g]), lc4 = *(const f32x4*)(&Lc[16 * a + 4 * g]);
 #pragma unroll
       for (int r = 0; r < 4; ++r) ar[4 * a + r] = (deadw || lc4[r] == INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s[r] * sc2 - lr4[r]);
     }
-    const bf16x8 d0 = rc_frag_cols(Do, 0, t, g), d1 = rc_frag_cols(Do, 1, t, g);
+    const bf16x8 d0 = frag_cols(Do, 0, t, g), d1 = frag_cols(Do, 1, t, g);
     __syncthreads();          // table visible
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
