@@ -1078,6 +1078,7 @@ int mi_pos_embed_sine(const uint8_t* mask, int B, int H, int W, int num_pos_feat
  * (prediction, target) pairs of SparseInstCriterion (loss/sparseinst_loss.py:123-187).  See csrc/sparseinst_ops.hip. */
 int mi_bilinear_resize_bf16(const void* x, int ldx, int N, int H, int W, int C, void* y, int ldy, int Ho, int Wo,
                             mi_stream_t s);
+/* (the backward gathers in a fixed order: no workspace; the float* argument is ignored and may be NULL) */
 int mi_bilinear_resize_bwd_bf16(const void* dy, int lddy, int N, int H, int W, int C, void* dx, int lddx, int Ho, int Wo,
                                 float* acc_ws_zeroed, mi_stream_t s);
 /* PyramidPoolingModule's pooling stages (transcoders/encoder_sparseinst.py:18-62: F.avg_pool2d(x, kernel = (kh, kw), stride =

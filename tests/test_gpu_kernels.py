@@ -487,31 +487,27 @@ def test_bn_backward_fused_matches_two_pass(C, npix, act, res):
 @pytest.mark.parametrize("N,H,W", [(2, 16, 24), (1, 6, 10), (3, 64, 96), (2, 8, 12), (2, 6, 32), (1, 70, 64), (2, 640, 640)])
 def test_focus_pack_float_and_uint8_bit_exact(N, H, W):
     """Focus (wrappers.py:202-220) from the float image and from the uint8 image, the 4-pixels-per-thread kernels (W % 8
-    == 0), the scalar ones and the row-staged uint8 kernel (W % 16 == 0; an odd number of output rows leaves half a row
-    pair): TL, BL, TR, BR x (c0, c1, c2) into 16-channel pixels, the 4 pad channels zero - exact"""
+    == 0), the scalar ones and the row-staged lane-pair uint8 kernel (W % 16 == 0; an odd number of output rows leaves part
+    of a row group): TL, BL, TR, BR x (c0, c1, c2) into 16-channel pixels, the 4 pad channels zero - exact"""
     lib = L.lib()
     g = torch.Generator().manual_seed(H * W)
     u8 = torch.randint(0, 256, (N, 3, H, W), generator=g, dtype=torch.uint8)
     f32 = u8.float()
     ref = torch.cat([f32[..., ::2, ::2], f32[..., 1::2, ::2], f32[..., ::2, 1::2], f32[..., 1::2, 1::2]], 1)   # [N,12,H/2,W/2]
     ref = ref.permute(0, 2, 3, 1)
-    import os
-    prev = os.environ.get("MI_FOCUS_ROWS")
-    try:
-        # uint8: the lane-pair-store kernel (round 6, the default), the row-staged kernel, the per-pixel kernel - forced
-        for src, fn, mode in ((f32.to(DEV), lib.mi_focus_pack, None), (u8.to(DEV), lib.mi_focus_pack_u8, "2"),
-                              (u8.to(DEV), lib.mi_focus_pack_u8, "1"), (u8.to(DEV), lib.mi_focus_pack_u8, "0")):
-            if mode is not None:
-                os.environ["MI_FOCUS_ROWS"] = mode
-            for ld in (16, 24):            # a contiguous output and a channel slice of a wider buffer
-                out = torch.full((N, H // 2, W // 2, ld), 5.0, dtype=torch.bfloat16, device=DEV)
-                L.check(fn(src.data_ptr(), N, H, W, out.data_ptr(), ld, sp()), "focus")
-                torch.cuda.synchronize()
-                o = out.float().cpu()
-                assert torch.equal(o[..., :12], ref) and torch.all(o[..., 12:16] == 0), (mode, ld)
-                assert torch.all(o[..., 16:] == 5.0)
-    finally:
-        if prev is None:
-            os.environ.pop("MI_FOCUS_ROWS", None)
-        else:
-            os.environ["MI_FOCUS_ROWS"] = prev
+    # the same uint8 image 2 bytes into its buffer: 2-byte but not 16-byte aligned, so the per-pixel uint8 kernel runs at
+    # every shape (an aligned image with W % 16 == 0 takes the lane-pair kernel)
+    buf = torch.zeros(u8.numel() + 16, dtype=torch.uint8, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    off2 = buf[2:2 + u8.numel()]
+    off2.copy_(u8.reshape(-1))
+    for src, fn, what in ((f32.to(DEV), lib.mi_focus_pack, "float"), (u8.to(DEV), lib.mi_focus_pack_u8, "uint8"),
+                          (off2, lib.mi_focus_pack_u8, "uint8 at +2 bytes")):
+        assert src.data_ptr() % 16 == (2 if src is off2 else 0)
+        for ld in (16, 24):            # a contiguous output and a channel slice of a wider buffer
+            out = torch.full((N, H // 2, W // 2, ld), 5.0, dtype=torch.bfloat16, device=DEV)
+            L.check(fn(src.data_ptr(), N, H, W, out.data_ptr(), ld, sp()), "focus")
+            torch.cuda.synchronize()
+            o = out.float().cpu()
+            assert torch.equal(o[..., :12], ref) and torch.all(o[..., 12:16] == 0), (what, ld)
+            assert torch.all(o[..., 16:] == 5.0)

@@ -85,50 +85,13 @@ __global__ __launch_bounds__(256) void focus_pack4_kernel(const T* __restrict__ 
   }
 }
 
-// The uint8 image, one BLOCK per pair of output rows: the six (channel, row parity) source rows of an output row arrive as
-// 16-byte loads (one per lane: W / 16 pieces per row) in LDS, then every thread assembles output pixels from six 2-byte LDS
-// reads and writes 32 contiguous bytes.  focus_pack4_kernel's global loads are 2 bytes per lane - 128 bytes per wave
-// instruction, 24 instructions per thread: 48.8 us for 72 MB in the captured step (1.5 TB/s).  Needs W % 16 == 0 and a
-// 16-byte aligned image (MI_FOCUS_ROWS=0: the per-pixel form).
-#define FOCUS_ROWS 2
-__global__ __launch_bounds__(256) void focus_pack_u8_rows_kernel(const uint8_t* __restrict__ img, int N, int H, int W,
-                                                                 __bf16* out, int ldo) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t srow[];      // [FOCUS_ROWS][3 channels][2 parities][W]
-  const int Ho = H / 2, Wo = W / 2;
-  const int rb = (Ho + FOCUS_ROWS - 1) / FOCUS_ROWS;
-  const int n = blockIdx.x / rb, oy0 = (blockIdx.x % rb) * FOCUS_ROWS;
-  const int per = W / 16;
-  for (int i = threadIdx.x; i < FOCUS_ROWS * 6 * per; i += 256) {
-    const int piece = i % per, rowi = i / per;        // rowi = (r * 3 + c) * 2 + dy
-    const int dy = rowi & 1, c = (rowi >> 1) % 3, r = rowi / 6;
-    if (oy0 + r < Ho)
-      *(uint4*)(srow + (size_t)rowi * W + piece * 16) =
-          *(const uint4*)(img + (((int64_t)n * 3 + c) * H + 2 * (oy0 + r) + dy) * W + piece * 16);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < FOCUS_ROWS * Wo; i += 256) {
-    const int r = i / Wo, ox = i - r * Wo;
-    if (oy0 + r >= Ho) break;
-    float f[16];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy) {
-        const unsigned short v = *(const unsigned short*)(srow + (size_t)((r * 3 + c) * 2 + dy) * W + 2 * ox);
-        f[dy * 3 + c] = (float)(v & 0xff);             // q: 0 TL, 1 BL, 2 TR, 3 BR (wrappers.py:202-220)
-        f[(2 + dy) * 3 + c] = (float)(v >> 8);
-      }
-    f[12] = f[13] = f[14] = f[15] = 0.f;
-    __bf16* op = out + ((size_t)(n * Ho + oy0 + r) * Wo + ox) * ldo;
-    *(bf16x8*)op = pack8(f);
-    *(bf16x8*)(op + 8) = pack8(f + 8);
-  }
-}
-
-// The same block geometry with the STORES laid out for whole lines (round 6): a lane PAIR writes one 32-byte output pixel,
-// even lane the first 16 bytes (TL c0..2, BL c0..2, TR c0..1), odd lane the second (TR c2, BR c0..2, four zero pads), so a
-// wave's store instruction covers 1 KB of consecutive addresses (ldo = 16) instead of 16 bytes out of every 32 twice
-// (focus_pack_u8_rows_kernel: 40 us for 52 MB of output in the captured step, 1.3 TB/s).  FOCUS_ROWS2 output rows per block.
+// The uint8 image, one BLOCK per FOCUS_ROWS2 output rows: the six (channel, row parity) source rows of an output row arrive
+// as 16-byte loads (one per lane: W / 16 pieces per row) in LDS, then the threads assemble output pixels from six 2-byte LDS
+// reads each.  focus_pack4_kernel's global loads are 2 bytes per lane - 128 bytes per wave instruction, 24 instructions per
+// thread: 48.8 us for 72 MB in the captured step (1.5 TB/s).  Needs W % 16 == 0 and a 16-byte aligned image.
+// The STORES are laid out for whole lines: a lane PAIR writes one 32-byte output pixel, even lane the first 16 bytes (TL
+// c0..2, BL c0..2, TR c0..1), odd lane the second (TR c2, BR c0..2, four zero pads), so a wave's store instruction covers
+// 1 KB of consecutive addresses (ldo = 16) instead of 16 bytes out of every 32 twice.
 template <int FOCUS_ROWS2>
 __global__ __launch_bounds__(256) void focus_pack_u8_pairs_kernel(const uint8_t* __restrict__ img, int N, int H, int W,
                                                                   __bf16* out, int ldo) {
@@ -174,27 +137,15 @@ extern "C" int mi_focus_pack_u8(const uint8_t* img, int N, int H, int W, void* o
              "focus_pack_u8: args");
   const int64_t total = (int64_t)N * (H / 2) * (W / 2);
   MI_REQUIRE(total < (1LL << 31) - (1 << 24), "focus_pack_u8: %lld output pixels exceed the 32-bit index", (long long)total);
-  // MI_FOCUS_ROWS: 2 (default) lane-pair stores, 1 the round-5 row kernel, 0 the per-pixel kernel (read per call: the
-  // equality test runs all three in one process)
-  const int rows_mode = getenv("MI_FOCUS_ROWS") ? atoi(getenv("MI_FOCUS_ROWS")) : 2;
-  if (rows_mode >= 2 && W % 16 == 0 && ((uintptr_t)img & 15) == 0 && W <= 4096) {
-    static const int th = getenv("MI_FOCUS_TH") ? atoi(getenv("MI_FOCUS_TH")) : 4;     // output rows per block (A/B knob: 1, 2, 4, 8)
-    const int R = th == 1 ? 1 : th == 2 ? 2 : th == 8 ? 8 : 4;
-    const int rb = (H / 2 + R - 1) / R;
-    const dim3 g((unsigned)(N * rb));
+  if (W % 16 == 0 && ((uintptr_t)img & 15) == 0 && W <= 4096) {
+    // output rows per block: 4; MI_FOCUS_TH=1 (read once) keeps the one-row form, which was 0.2 us ahead back to back and
+    // 0.3 us behind with cold caches, as in the step (profiles/loss_misc_forms_removal_ab.txt)
+    static const int R = getenv("MI_FOCUS_TH") && atoi(getenv("MI_FOCUS_TH")) == 1 ? 1 : 4;
+    const dim3 g((unsigned)(N * ((H / 2 + R - 1) / R)));
     const size_t lds = (size_t)R * 6 * W;
     if (R == 1) hipLaunchKernelGGL(focus_pack_u8_pairs_kernel<1>, g, dim3(256), lds, (hipStream_t)st, img, N, H, W, (__bf16*)out, ldo);
-    else if (R == 2) hipLaunchKernelGGL(focus_pack_u8_pairs_kernel<2>, g, dim3(256), lds, (hipStream_t)st, img, N, H, W, (__bf16*)out, ldo);
-    else if (R == 8) hipLaunchKernelGGL(focus_pack_u8_pairs_kernel<8>, g, dim3(256), lds, (hipStream_t)st, img, N, H, W, (__bf16*)out, ldo);
     else hipLaunchKernelGGL(focus_pack_u8_pairs_kernel<4>, g, dim3(256), lds, (hipStream_t)st, img, N, H, W, (__bf16*)out, ldo);
     MI_CHECK_LAUNCH("focus_pack_u8 (pairs)");
-    return MI_OK;
-  }
-  if (rows_mode && W % 16 == 0 && ((uintptr_t)img & 15) == 0 && W <= 4096) {
-    const int rb = (H / 2 + FOCUS_ROWS - 1) / FOCUS_ROWS;
-    hipLaunchKernelGGL(focus_pack_u8_rows_kernel, dim3((unsigned)(N * rb)), dim3(256), (size_t)FOCUS_ROWS * 6 * W, (hipStream_t)st, img,
-                       N, H, W, (__bf16*)out, ldo);
-    MI_CHECK_LAUNCH("focus_pack_u8 (rows)");
     return MI_OK;
   }
   hipLaunchKernelGGL(focus_pack4_kernel<uint8_t>, dim3(ew_blocks((total + 3) / 4)), dim3(256), 0, (hipStream_t)st, img, N, H,
@@ -495,7 +446,7 @@ __global__ __launch_bounds__(SPP_T) void spp_fwd_plane_kernel(const __bf16* __re
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int HW = H * W, C = C8 * 8;
   bf16x8* Xp = (bf16x8*)smem;          // [HW] input plane
-  bf16x8* Hv = Xp + HW;                // [HW] horizontal max values of the current k
+  bf16x8* Hv = Xp + HW;                // [HW] horizontal max values
   uint64_t* Hc = (uint64_t*)(Hv + HW); // [HW] their dx codes
   // a block touches 16 bytes of every 128-byte line of its plane; the 8 blocks that share those lines (adjacent c8) must sit
   // on the SAME XCD to meet in its L2 - block ids go round-robin over the 8 XCDs, so give each XCD a contiguous range of
@@ -506,61 +457,57 @@ __global__ __launch_bounds__(SPP_T) void spp_fwd_plane_kernel(const __bf16* __re
   const __bf16* xb = x + ((int64_t)n * HW) * ldx + c8 * 8;
   for (int p = threadIdx.x; p < HW; p += SPP_T) Xp[p] = *(const bf16x8*)(xb + (int64_t)p * ldx);
   __syncthreads();
-  // gridDim.y == 3 (round 6): the three window sizes are three BLOCKS of the plane (each loads it: 3.3 MB in all) - the
-  // kernel is bound by the serial chain inside a block (window loads, barrier, window loads per size), and a third of the
-  // chain on three times as many resident blocks hides it better than one block walking all three
-  const int k_lo = gridDim.y == 3 ? (int)blockIdx.y : 0, k_hi = gridDim.y == 3 ? (int)blockIdx.y + 1 : 3;
-  for (int k = k_lo; k < k_hi; ++k) {
-    const int r = 2 + 2 * k;
-    for (int p = threadIdx.x; p < HW; p += SPP_T) {
-      const int py = p / W, px = p - py * W;
-      float m[8];
-      uint8_t am[8];
+  // the three window sizes are three BLOCKS of the plane (gridDim.y == 3; each loads it: 3.3 MB in all) - the kernel is
+  // bound by the serial chain inside a block (window loads, barrier, window loads), and a third of the chain on three
+  // times as many resident blocks hides it better than one block walking all three sizes
+  const int k = blockIdx.y, r = 2 + 2 * k;
+  for (int p = threadIdx.x; p < HW; p += SPP_T) {
+    const int py = p / W, px = p - py * W;
+    float m[8];
+    uint8_t am[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; am[e] = 6; }
-      for (int dx = -r; dx <= r; ++dx) {
-        const int xx = px + dx;
-        if (xx < 0 || xx >= W) continue;
-        const bf16x8 v = Xp[py * W + xx];
+    for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; am[e] = 6; }
+    for (int dx = -r; dx <= r; ++dx) {
+      const int xx = px + dx;
+      if (xx < 0 || xx >= W) continue;
+      const bf16x8 v = Xp[py * W + xx];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float f = (float)v[e];
-          if (f > m[e]) { m[e] = f; am[e] = (uint8_t)(dx + 6); }
-        }
+      for (int e = 0; e < 8; ++e) {
+        const float f = (float)v[e];
+        if (f > m[e]) { m[e] = f; am[e] = (uint8_t)(dx + 6); }
       }
-      Hv[p] = pack8(m);
-      uint64_t pk = 0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pk |= (uint64_t)am[e] << (8 * e);
-      Hc[p] = pk;
-      *(uint64_t*)(idx + ((int64_t)(3 + k) * npix + (int64_t)n * HW + p) * C + c8 * 8) = pk;
     }
-    __syncthreads();
-    __bf16* yk = k == 0 ? y5 : (k == 1 ? y9 : y13);
-    for (int p = threadIdx.x; p < HW; p += SPP_T) {
-      const int py = p / W, px = p - py * W;
-      float m[8];
-      uint8_t am[8];
+    Hv[p] = pack8(m);
+    uint64_t pk = 0;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; am[e] = 6; }
-      for (int dy = -r; dy <= r; ++dy) {
-        const int yy = py + dy;
-        if (yy < 0 || yy >= H) continue;
-        const bf16x8 v = Hv[yy * W + px];
+    for (int e = 0; e < 8; ++e) pk |= (uint64_t)am[e] << (8 * e);
+    Hc[p] = pk;
+    *(uint64_t*)(idx + ((int64_t)(3 + k) * npix + (int64_t)n * HW + p) * C + c8 * 8) = pk;
+  }
+  __syncthreads();
+  __bf16* yk = k == 0 ? y5 : (k == 1 ? y9 : y13);
+  for (int p = threadIdx.x; p < HW; p += SPP_T) {
+    const int py = p / W, px = p - py * W;
+    float m[8];
+    uint8_t am[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float f = (float)v[e];
-          if (f > m[e]) { m[e] = f; am[e] = (uint8_t)(dy + 6); }
-        }
+    for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; am[e] = 6; }
+    for (int dy = -r; dy <= r; ++dy) {
+      const int yy = py + dy;
+      if (yy < 0 || yy >= H) continue;
+      const bf16x8 v = Hv[yy * W + px];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float f = (float)v[e];
+        if (f > m[e]) { m[e] = f; am[e] = (uint8_t)(dy + 6); }
       }
-      const int64_t pix = (int64_t)n * HW + p;
-      *(bf16x8*)(yk + pix * ldy + c8 * 8) = pack8(m);
-      uint64_t pk = 0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pk |= (uint64_t)am[e] << (8 * e);
-      *(uint64_t*)(idx + ((int64_t)k * npix + pix) * C + c8 * 8) = pk;
     }
-    __syncthreads();
+    const int64_t pix = (int64_t)n * HW + p;
+    *(bf16x8*)(yk + pix * ldy + c8 * 8) = pack8(m);
+    uint64_t pk = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pk |= (uint64_t)am[e] << (8 * e);
+    *(uint64_t*)(idx + ((int64_t)k * npix + pix) * C + c8 * 8) = pk;
   }
 }
 
@@ -662,9 +609,7 @@ extern "C" int mi_spp_pool_fwd(const void* x, int ldx, void* y5, void* y9, void*
     hipFuncSetAttribute((const void*)spp_bwd_plane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  const char* sk = getenv("MI_SPP_SPLIT");        // (read per call: the tests compare the two forms in one process)
-  const int split = sk ? atoi(sk) : 1;
-  hipLaunchKernelGGL(spp_fwd_plane_kernel, dim3(N * (C / 8), split ? 3 : 1), dim3(SPP_T), lds, (hipStream_t)st, (const __bf16*)x, ldx,
+  hipLaunchKernelGGL(spp_fwd_plane_kernel, dim3(N * (C / 8), 3), dim3(SPP_T), lds, (hipStream_t)st, (const __bf16*)x, ldx,
                      (__bf16*)y5, (__bf16*)y9, (__bf16*)y13, ldy, idx, N, H, W, C / 8);
   MI_CHECK_LAUNCH("spp_fwd");
   return MI_OK;

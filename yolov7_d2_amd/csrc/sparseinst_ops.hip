@@ -7,7 +7,6 @@
 //     (compute_mask_iou :19-28, dice_loss :38-47); a second pass writes d(loss)/d(mask logits).
 // The convolutions, the IAM aggregation / dynamic mask "bmm"s and the matcher's dice-score matmul run on the conv /
 // wgrad MFMA kernels (modeling/sparseinst.py), the assignment on mi_lsap.
-#include <stdlib.h>
 #include <string.h>
 #include "common.h"
 
@@ -15,7 +14,6 @@
 struct ResizeK {
   const __bf16* x;
   __bf16* y;
-  float* acc;     // backward: fp32 [N][H][W][C] accumulator
   int ldx, ldy, N, H, W, Ho, Wo, C8;
   float sh, sw;   // H / Ho, W / Wo
 };
@@ -54,36 +52,8 @@ __global__ __launch_bounds__(256) void resize_fwd_kernel(const ResizeK p) {
   }
 }
 
-// backward: every output-gradient pixel adds its four weighted contributions into the fp32 accumulator (hardware
-// float atomics), a second launch rounds the accumulator to bf16
-__global__ __launch_bounds__(256) void resize_bwd_kernel(const ResizeK p) {   // p.x = dy (Ho x Wo), p.acc = dx accumulator
-  const int64_t total = (int64_t)p.N * p.Ho * p.Wo * p.C8;
-  const int C = p.C8 * 8;
-  for (int64_t idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-    const int c8 = (int)(idx % p.C8);
-    int64_t r = idx / p.C8;
-    const int ox = (int)(r % p.Wo); r /= p.Wo;
-    const int oy = (int)(r % p.Ho);
-    const int n = (int)(r / p.Ho);
-    int y0, y1, x0, x1;
-    float ly, lx;
-    src_index(oy, p.sh, p.H, &y0, &y1, &ly);
-    src_index(ox, p.sw, p.W, &x0, &x1, &lx);
-    const bf16x8 g = *(const bf16x8*)(p.x + (((int64_t)n * p.Ho + oy) * p.Wo + ox) * p.ldx + c8 * 8);
-    float* a = p.acc + ((int64_t)n * p.H * p.W) * C + c8 * 8;
-    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float ge = (float)g[e];
-      atomicAdd(a + ((int64_t)y0 * p.W + x0) * C + e, w00 * ge);
-      atomicAdd(a + ((int64_t)y0 * p.W + x1) * C + e, w01 * ge);
-      atomicAdd(a + ((int64_t)y1 * p.W + x0) * C + e, w10 * ge);
-      atomicAdd(a + ((int64_t)y1 * p.W + x1) * C + e, w11 * ge);
-    }
-  }
-}
-// gather form: an input pixel collects, in a fixed order, the weighted out-gradients of every output pixel whose bilinear
-// footprint contains it - no atomics, no fp32 accumulator tensor, no rounding pass, deterministic.  (The scatter form above
+// backward, a gather: an input pixel collects, in a fixed order, the weighted out-gradients of every output pixel whose
+// bilinear footprint contains it - no atomics, no fp32 accumulator tensor, no rounding pass, deterministic.  (A scatter
 // was 32 float atomics per output element: 1.03 ms per call, a quarter of the SparseInst step.)  The candidate output rows /
 // columns of input index i are those with source coordinate in (i - 1, i + 1); each candidate's (i0, i1, l1) is recomputed
 // with the forward's own src_index, so the two passes agree bit for bit on which pixels touch which.
@@ -189,17 +159,6 @@ __global__ __launch_bounds__(256) void resize_bwd_pixel_kernel(const ResizeK p) 
     *(bf16x8*)(p.y + (((int64_t)n * p.H + iy) * p.W + ix) * p.ldy + c8 * 8) = pack8(acc);
   }
 }
-__global__ __launch_bounds__(256) void f32_to_bf16_rows_kernel(const float* __restrict__ a, __bf16* o, int ldo, int64_t npix, int C8) {
-  const int64_t total = npix * C8;
-  for (int64_t idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-    const int c8 = (int)(idx % C8);
-    const int64_t px = idx / C8;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = a[px * C8 * 8 + c8 * 8 + e];
-    *(bf16x8*)(o + px * ldo + c8 * 8) = pack8(v);
-  }
-}
 
 static int nblocks(int64_t total) {
   int64_t b = (total + 1023) / 1024;
@@ -220,38 +179,26 @@ extern "C" int mi_bilinear_resize_bf16(const void* x, int ldx, int N, int H, int
   MI_CHECK_LAUNCH("bilinear_resize");
   return MI_OK;
 }
-// dy: [N][Ho][Wo][C] (lddy) -> dx: [N][H][W][C] (lddx); acc_ws: unused (may be NULL) - only MI_RESIZE_BWD_SCATTER=1, the
-// first atomic form, needs it: fp32 N*H*W*C, zeroed by the caller
+// dy: [N][Ho][Wo][C] (lddy) -> dx: [N][H][W][C] (lddx); acc_ws is ignored (may be NULL)
 extern "C" int mi_bilinear_resize_bwd_bf16(const void* dy, int lddy, int N, int H, int W, int C, void* dx, int lddx, int Ho,
                                            int Wo, float* acc_ws, mi_stream_t st) {
+  (void)acc_ws;
   MI_REQUIRE(dy && dx && C % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0, "bilinear_resize_bwd: args");
   ResizeK k;
   memset(&k, 0, sizeof(k));
-  k.x = (const __bf16*)dy; k.acc = acc_ws; k.ldx = lddy; k.N = N; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo; k.C8 = C / 8;
-  k.sh = (float)H / (float)Ho; k.sw = (float)W / (float)Wo;
+  k.x = (const __bf16*)dy; k.y = (__bf16*)dx; k.ldx = lddy; k.ldy = lddx; k.N = N; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo;
+  k.C8 = C / 8; k.sh = (float)H / (float)Ho; k.sw = (float)W / (float)Wo;
   hipStream_t s = (hipStream_t)st;
-  const char* sc = getenv("MI_RESIZE_BWD_SCATTER");      // (the first, atomic form: kept for comparison; it needs acc_ws zeroed)
-  if (!(sc && atoi(sc))) {
-    k.y = (__bf16*)dx; k.ldy = lddx;
-    // window of one input pixel ~ (2 Ho / H + 3) x (2 Wo / W + 3) candidates (clamped to the map)
-    const float wy = 2.f / k.sh + 3.f, wx = 2.f / k.sw + 3.f;
-    const float cand = (wy < (float)Ho ? wy : (float)Ho) * (wx < (float)Wo ? wx : (float)Wo);
-    static const int px_mode = getenv("MI_RESIZE_BWD_PIXEL") ? atoi(getenv("MI_RESIZE_BWD_PIXEL")) : 1;   // 0: round-4 form everywhere
-    if (px_mode && cand >= 64.f && (int64_t)N * H * W <= 65536 && k.C8 <= 256) {
-      hipLaunchKernelGGL(resize_bwd_pixel_kernel, dim3((unsigned)((int64_t)N * H * W)), dim3(256), 0, s, k);
-      MI_CHECK_LAUNCH("bilinear_resize_bwd (block per pixel)");
-      return MI_OK;
-    }
-    hipLaunchKernelGGL(resize_bwd_gather_kernel, dim3(nblocks((int64_t)N * H * W * k.C8)), dim3(256), 0, s, k);
-    MI_CHECK_LAUNCH("bilinear_resize_bwd");
+  // window of one input pixel ~ (2 Ho / H + 3) x (2 Wo / W + 3) candidates (clamped to the map)
+  const float wy = 2.f / k.sh + 3.f, wx = 2.f / k.sw + 3.f;
+  const float cand = (wy < (float)Ho ? wy : (float)Ho) * (wx < (float)Wo ? wx : (float)Wo);
+  if (cand >= 64.f && (int64_t)N * H * W <= 65536 && k.C8 <= 256) {
+    hipLaunchKernelGGL(resize_bwd_pixel_kernel, dim3((unsigned)((int64_t)N * H * W)), dim3(256), 0, s, k);
+    MI_CHECK_LAUNCH("bilinear_resize_bwd (block per pixel)");
     return MI_OK;
   }
-  MI_REQUIRE(acc_ws, "bilinear_resize_bwd: the scatter form needs the fp32 accumulator");
-  hipLaunchKernelGGL(resize_bwd_kernel, dim3(nblocks((int64_t)N * Ho * Wo * k.C8)), dim3(256), 0, s, k);
+  hipLaunchKernelGGL(resize_bwd_gather_kernel, dim3(nblocks((int64_t)N * H * W * k.C8)), dim3(256), 0, s, k);
   MI_CHECK_LAUNCH("bilinear_resize_bwd");
-  hipLaunchKernelGGL(f32_to_bf16_rows_kernel, dim3(nblocks((int64_t)N * H * W * k.C8)), dim3(256), 0, s, acc_ws,
-                     (__bf16*)dx, lddx, (int64_t)N * H * W, k.C8);
-  MI_CHECK_LAUNCH("bilinear_resize_bwd_round");
   return MI_OK;
 }
 

@@ -11,7 +11,6 @@
 // The reference loops over images and ground truths on the host with .item() syncs; here the
 // batch is processed by four launches.  Compile with -ffp-contract=off: the float expressions keep
 // the reference's operation order so near-ties resolve the same way.
-#include <stdlib.h>
 #include "common.h"
 #include "iou_v6.h"
 
@@ -35,9 +34,8 @@ struct LossK {
   float* partial_l1;   // [nblk] block sums of the L1 term
   // the YOLOv6 head's form of the same loss (ComputeLoss, head/yolov6_head.py:315-754): configurable SimOTA weights /
   // centre radius and an IOUlossV6 box loss; the YOLOX values are 2.5, 1, 3, 5 and box loss 1 - iou^2 (iou_type 0)
-  float center_radius, cls_weight, iou_weight, reg_weight;
-  int dbg;             // timing experiments (MI_SIMOTA_DBG): early exits of the dynamic-k kernel
   int iou_type;        // 0: IOUloss "iou" of the YOLOX head; 1..4: IOUlossV6 giou / diou / ciou / siou (eps 1e-7)
+  float center_radius, cls_weight, iou_weight, reg_weight;
 };
 
 // l1 target of one foreground anchor (yolox_head.py:443-448; eps = 1e-8)
@@ -50,19 +48,6 @@ __device__ __forceinline__ void l1_target(const float* lab, float gx_, float gy_
 
 __device__ __forceinline__ float clamp_log(float v) { return fmaxf(logf(v), -100.0f); }
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// number of valid labels: rows with sum > 0 (yolox_head.py:295)
-__device__ int count_labels(const float* lab, int max_labels) {
-  int n = 0;
-  for (int r = 0; r < max_labels; ++r) {
-    float s = lab[r * 5 + 0] + lab[r * 5 + 1];
-    s = s + lab[r * 5 + 2];
-    s = s + lab[r * 5 + 3];
-    s = s + lab[r * 5 + 4];
-    if (s > 0.f) ++n;
-  }
-  return n;
-}
 
 // ---- kernel 1: candidates, pairwise IoU and cost
 // what the cost of one (candidate anchor, gt) pair needs of the anchor
@@ -98,7 +83,7 @@ __device__ __forceinline__ float simota_class_sum(const LossK& p, const float* p
   }
   return S;
 }
-// cost / IoU of one pair, stored at [g][a] (yolox_head.py:487-547)
+// cost / IoU of one pair (yolox_head.py:487-547)
 __device__ __forceinline__ void simota_cost_pair(const LossK& p, const float* slab, int g, const CandRec& r, float* costp, float* ioup) {
   const float xc = r.xc, yc = r.yc, st = r.st, px = r.px, py = r.py, pw = r.pw, ph = r.ph;
   const float area_b = pw * ph;
@@ -127,58 +112,42 @@ __device__ __forceinline__ void simota_cost_pair(const LossK& p, const float* sl
   *costp = cost;
   *ioup = iou;
 }
-// one candidate anchor, the round-5 way: everything by its own thread
-__device__ __forceinline__ void simota_cost_candidate(const LossK& p, const float* slab, int G, int b, int a) {
-  CandRec r;
-  simota_cand_decode(p, b, a, r);
-  r.S = simota_class_sum(p, r.pr, r.so);
-  const size_t rowstride = (size_t)p.A;
-  float* costp = p.cost + (size_t)b * p.gmax * rowstride + a;
-  float* ioup = p.iou + (size_t)b * p.gmax * rowstride + a;
-  for (int g = 0; g < G; ++g) simota_cost_pair(p, slab, g, r, costp + g * rowstride, ioup + g * rowstride);
-}
 
-// FORM 0: the round-5 kernel (thread 0 counts the labels; a candidate's thread does all of its work - in waves a third
-// of whose lanes hold a candidate with COCO-sized boxes).
-// FORM 1: the label count across the threads; the block's candidates gathered into a list, the first ncand threads take
-// one each.
-// FORM 2: FORM 1, and (a) the class term is formed with the CLASSES across the lanes - 16 lanes take one candidate's row
-// (64 contiguous bytes per load instead of 64 lanes in 64 different rows 340 bytes apart), the terms go to LDS and the
-// candidate's thread adds them up in class order: the same float sum as the loop over its own row; (b) the (candidate, gt)
-// PAIRS are dealt to all 256 threads (an image's blocks hold 30 - 250 candidates and up to gmax ground truths).
-// Same expressions per class term / pair: identical outputs.
+// The label count is taken across the threads and the block's candidates are gathered into a list.
+// CLASS_LANES (the terms of 16 candidates fit SIMOTA_TERM_FLOATS: fewer than 640 classes): (a) the class term is formed with
+// the CLASSES across the lanes - 16 lanes take one candidate's row (64 contiguous bytes per load instead of 64 lanes in 64
+// different rows 340 bytes apart), the terms go to LDS and the candidate's thread adds them up in class order: the same
+// float sum as the loop over its own row; (b) the (candidate, gt) PAIRS are dealt to all 256 threads (an image's blocks
+// hold 30 - 250 candidates and up to gmax ground truths).
+// Otherwise the first ncand threads take one candidate each and do all of its work.
+// Same expressions per class term / pair either way: identical outputs.
 #define SIMOTA_TERM_FLOATS 10240
-template <int FORM, int NT = 256>
-__global__ __launch_bounds__(NT) void simota_cost_kernel(const LossK p) {
-  constexpr int NW = NT / 64;
-  extern __shared__ float slab[];  // [gmax][5] (FORM 2: + [SIMOTA_TERM_FLOATS] class terms)
+template <bool CLASS_LANES>
+__global__ __launch_bounds__(256) void simota_cost_kernel(const LossK p) {
+  constexpr int NT = 256, NW = NT / 64;
+  extern __shared__ float slab[];  // [gmax][5] (CLASS_LANES: + [SIMOTA_TERM_FLOATS] class terms)
   __shared__ int s_ngt;
-  __shared__ CandRec s_rec[FORM == 2 ? NT : 1];
+  __shared__ CandRec s_rec[CLASS_LANES ? NT : 1];
   __shared__ int s_wn[NW];
   __shared__ unsigned short s_list[NT];
   const int b = blockIdx.y, tid = threadIdx.x;
   const float* lab = p.labels + (size_t)b * p.max_labels * 5;
-  if constexpr (FORM == 0) {
-    if (tid == 0) s_ngt = count_labels(lab, p.max_labels);
-  } else {
-    // number of valid labels: rows with sum > 0 (yolox_head.py:295; count_labels across the threads)
-    if (tid == 0) s_ngt = 0;
-    __syncthreads();
-    int n = 0;
-    for (int r = tid; r < p.max_labels; r += NT) {
-      float sm = lab[r * 5 + 0] + lab[r * 5 + 1];
-      sm = sm + lab[r * 5 + 2];
-      sm = sm + lab[r * 5 + 3];
-      sm = sm + lab[r * 5 + 4];
-      n += sm > 0.f ? 1 : 0;
-    }
-    if (n) atomicAdd(&s_ngt, n);
+  // number of valid labels: rows with sum > 0 (yolox_head.py:295)
+  if (tid == 0) s_ngt = 0;
+  __syncthreads();
+  int nlab = 0;
+  for (int r = tid; r < p.max_labels; r += NT) {
+    float sm = lab[r * 5 + 0] + lab[r * 5 + 1];
+    sm = sm + lab[r * 5 + 2];
+    sm = sm + lab[r * 5 + 3];
+    sm = sm + lab[r * 5 + 4];
+    nlab += sm > 0.f ? 1 : 0;
   }
+  if (nlab) atomicAdd(&s_ngt, nlab);
   for (int i = tid; i < p.gmax * 5; i += NT) slab[i] = lab[i];
   __syncthreads();
   const int G = s_ngt < p.gmax ? s_ngt : p.gmax;
   if (tid == 0 && blockIdx.x == 0) p.ngt[b] = G;
-  if (p.dbg == 4) return;
   const int a = blockIdx.x * NT + tid;
   bool cand = false;
   if (a < p.A) {
@@ -209,89 +178,91 @@ __global__ __launch_bounds__(NT) void simota_cost_kernel(const LossK p) {
       }
     }
   }
-  if (p.dbg == 5) return;
-  if constexpr (FORM == 0) {
-    if (cand) simota_cost_candidate(p, slab, G, b, a);
-  } else {
-    const unsigned long long m = __ballot(cand);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) s_wn[wave] = __popcll(m);
-    __syncthreads();
-    int off = 0, total = 0;
+  const unsigned long long m = __ballot(cand);
+  const int lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) s_wn[wave] = __popcll(m);
+  __syncthreads();
+  int off = 0, total = 0;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      if (w < wave) off += s_wn[w];
-      total += s_wn[w];
-    }
-    if (cand) s_list[off + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)tid;
-    __syncthreads();
-    if constexpr (FORM == 1) {
-      if (tid < total) simota_cost_candidate(p, slab, G, b, blockIdx.x * NT + s_list[tid]);
-    } else {
-      float* const s_term = slab + p.gmax * 5;
-      const int ncls = p.ncls, ld = ncls + 1, CH = SIMOTA_TERM_FLOATS / ld;   // (host: CH >= 16)
-      CandRec rec;
-      if (tid < total) {
-        simota_cand_decode(p, b, blockIdx.x * NT + s_list[tid], rec);
-        s_rec[tid].so = rec.so;
-        s_rec[tid].pr = rec.pr;
+  for (int w = 0; w < NW; ++w) {
+    if (w < wave) off += s_wn[w];
+    total += s_wn[w];
+  }
+  if (cand) s_list[off + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)tid;
+  __syncthreads();
+  const size_t rowstride = (size_t)p.A;   // cost / IoU of a pair are stored at [g][a]
+  float* const cost0 = p.cost + (size_t)b * p.gmax * rowstride + (size_t)blockIdx.x * NT;
+  float* const iou0 = p.iou + (size_t)b * p.gmax * rowstride + (size_t)blockIdx.x * NT;
+  if constexpr (!CLASS_LANES) {
+    if (tid < total) {
+      CandRec r;
+      simota_cand_decode(p, b, blockIdx.x * NT + s_list[tid], r);
+      r.S = simota_class_sum(p, r.pr, r.so);
+      for (int g = 0; g < G; ++g) {
+        const size_t o = (size_t)g * rowstride + s_list[tid];
+        simota_cost_pair(p, slab, g, r, cost0 + o, iou0 + o);
       }
-      __syncthreads();
-      const int grp = tid >> 4, gl = tid & 15;
-      for (int c0 = 0; c0 < total; c0 += CH) {
-        const int n = total - c0 < CH ? total - c0 : CH;
-        // four candidates x eight logits per 16-lane group are loaded before the first is used: one load per iteration is a
-        // chain of dependent HBM round trips (a group walks ~8 candidates x 5 loads)
-        for (int ci0 = grp; ci0 < n; ci0 += NT / 4) {
-          for (int cb = 0; cb < ncls; cb += 128) {
-            float lg[4][8];
+    }
+  } else {
+    float* const s_term = slab + p.gmax * 5;
+    const int ncls = p.ncls, ld = ncls + 1, CH = SIMOTA_TERM_FLOATS / ld;   // (host: CH >= 16)
+    CandRec rec;
+    if (tid < total) {
+      simota_cand_decode(p, b, blockIdx.x * NT + s_list[tid], rec);
+      s_rec[tid].so = rec.so;
+      s_rec[tid].pr = rec.pr;
+    }
+    __syncthreads();
+    const int grp = tid >> 4, gl = tid & 15;
+    for (int c0 = 0; c0 < total; c0 += CH) {
+      const int n = total - c0 < CH ? total - c0 : CH;
+      // four candidates x eight logits per 16-lane group are loaded before the first is used: one load per iteration is a
+      // chain of dependent HBM round trips (a group walks ~8 candidates x 5 loads)
+      for (int ci0 = grp; ci0 < n; ci0 += NT / 4) {
+        for (int cb = 0; cb < ncls; cb += 128) {
+          float lg[4][8];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int ci = ci0 + (NT / 16) * u;
-              const float* pr = s_rec[c0 + (ci < n ? ci : 0)].pr + 5;
+          for (int u = 0; u < 4; ++u) {
+            const int ci = ci0 + (NT / 16) * u;
+            const float* pr = s_rec[c0 + (ci < n ? ci : 0)].pr + 5;
 #pragma unroll
-              for (int q = 0; q < 8; ++q) {
-                const int c = cb + gl + 16 * q;
-                lg[u][q] = (ci < n && c < ncls) ? pr[c] : 0.f;
-              }
+            for (int q = 0; q < 8; ++q) {
+              const int c = cb + gl + 16 * q;
+              lg[u][q] = (ci < n && c < ncls) ? pr[c] : 0.f;
             }
+          }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int ci = ci0 + (NT / 16) * u;
-              const float so = s_rec[c0 + (ci < n ? ci : 0)].so;
+          for (int u = 0; u < 4; ++u) {
+            const int ci = ci0 + (NT / 16) * u;
+            const float so = s_rec[c0 + (ci < n ? ci : 0)].so;
 #pragma unroll
-              for (int q = 0; q < 8; ++q) {
-                const int c = cb + gl + 16 * q;
-                if (ci < n && c < ncls) {
-                  const float pc = sqrtf(sigmoid_ref(lg[u][q]) * so);
-                  s_term[ci * ld + c] = clamp_log(1.0f - pc);
-                }
+            for (int q = 0; q < 8; ++q) {
+              const int c = cb + gl + 16 * q;
+              if (ci < n && c < ncls) {
+                const float pc = sqrtf(sigmoid_ref(lg[u][q]) * so);
+                s_term[ci * ld + c] = clamp_log(1.0f - pc);
               }
             }
           }
         }
-        __syncthreads();
-        if (tid >= c0 && tid < c0 + n) {
-          float S = 0.f;
-          for (int c = 0; c < ncls; ++c) S += s_term[(tid - c0) * ld + c];
-          rec.S = S;
-        }
-        __syncthreads();
       }
-      if (p.dbg == 6) return;
-      if (tid < total) s_rec[tid] = rec;
       __syncthreads();
-      // pairs: idx = g * total + ci (exact split: (idx + 0.5) / total is at least 0.5 / 256 away from an integer)
-      const float rt = 1.0f / (float)total;
-      const size_t rowstride = (size_t)p.A;
-      float* const cost0 = p.cost + (size_t)b * p.gmax * rowstride + (size_t)blockIdx.x * NT;
-      float* const iou0 = p.iou + (size_t)b * p.gmax * rowstride + (size_t)blockIdx.x * NT;
-      for (int idx = tid; idx < total * G; idx += NT) {
-        const int g = (int)(((float)idx + 0.5f) * rt);
-        const int ci = idx - g * total;
-        const size_t o = (size_t)g * rowstride + s_list[ci];
-        simota_cost_pair(p, slab, g, s_rec[ci], cost0 + o, iou0 + o);
+      if (tid >= c0 && tid < c0 + n) {
+        float S = 0.f;
+        for (int c = 0; c < ncls; ++c) S += s_term[(tid - c0) * ld + c];
+        rec.S = S;
       }
+      __syncthreads();
+    }
+    if (tid < total) s_rec[tid] = rec;
+    __syncthreads();
+    // pairs: idx = g * total + ci (exact split: (idx + 0.5) / total is at least 0.5 / 256 away from an integer)
+    const float rt = 1.0f / (float)total;
+    for (int idx = tid; idx < total * G; idx += NT) {
+      const int g = (int)(((float)idx + 0.5f) * rt);
+      const int ci = idx - g * total;
+      const size_t o = (size_t)g * rowstride + s_list[ci];
+      simota_cost_pair(p, slab, g, s_rec[ci], cost0 + o, iou0 + o);
     }
   }
 }
@@ -312,15 +283,30 @@ __device__ __forceinline__ bool kv_after(float v, int i, float lv, int li) {
   if (DESC) return v < lv || (v == lv && i > li);
   return v > lv || (v == lv && i > li);
 }
+// (bitwise | and &: no short-circuit branches inside the rank loops)
 template <bool DESC>
-__device__ KV block_select(const float* row, int A, float lv, int li, float invalid_lo, float invalid_hi, KV* sred) {
+__device__ __forceinline__ bool kv_valid(float v) {   // IoU rows: a candidate (iou >= 0); cost rows: below SIMOTA_INF
+  if (DESC) return !((v <= -0.5f) | (v >= INFINITY));
+  return !((v <= -INFINITY) | (v >= SIMOTA_INF));
+}
+// One ordered selection: the block's best valid element strictly after (lv, li) in the total order (li < 0: the best of
+// all; i < 0 in the result: none left).  row(j, a) is the row's element a = tid + 256 * j: NV registers per thread (the row
+// was read from HBM/L2 once; the scan is unrolled) or, NV == 0, a load from the row's pointer.
+template <bool DESC, int NV, class Row>
+__device__ __forceinline__ KV block_select(const Row& row, int A, float lv, int li, KV* sred) {
   float bv = 0.f;
   int bi = -1;
-  for (int a = threadIdx.x; a < A; a += 256) {
-    const float v = row[a];
-    if (v <= invalid_lo || v >= invalid_hi) continue;
-    if (!kv_after<DESC>(v, a, lv, li)) continue;
+  const auto take = [&](int j, int a) {
+    const float v = row(j, a);
+    if (!kv_valid<DESC>(v) || !kv_after<DESC>(v, a, lv, li)) return;
     if (kv_better<DESC>(v, a, bv, bi)) { bv = v; bi = a; }
+  };
+  if constexpr (NV > 0) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+      if ((int)threadIdx.x + 256 * j < A) take(j, threadIdx.x + 256 * j);
+  } else {
+    for (int a = threadIdx.x; a < A; a += 256) take(0, a);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -337,69 +323,29 @@ __device__ KV block_select(const float* row, int A, float lv, int li, float inva
     if (sred[w].i >= 0 && kv_better<DESC>(sred[w].v, sred[w].i, best.v, best.i)) best = sred[w];
   return best;
 }
-
-// register-resident variant: the row is read from HBM/L2 once (NV values per thread, element a = tid + 256*j),
-// the ~20 ordered selections then scan registers.  Same total order as block_select (ties -> smaller index).
-template <bool DESC, int NV>
-__device__ __forceinline__ KV block_select_reg(const float (&vals)[NV], int A, float lv, int li, float invalid_lo,
-                                               float invalid_hi, KV* sred) {
-  float bv = 0.f;
-  int bi = -1;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int a = threadIdx.x + 256 * j;
-    const float v = vals[j];
-    if (a >= A || v <= invalid_lo || v >= invalid_hi) continue;
-    if (!kv_after<DESC>(v, a, lv, li)) continue;
-    if (kv_better<DESC>(v, a, bv, bi)) { bv = v; bi = a; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (oi >= 0 && kv_better<DESC>(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sred[wave].v = bv; sred[wave].i = bi; }
-  __syncthreads();
-  KV best = sred[0];
-  for (int w = 1; w < 4; ++w)
-    if (sred[w].i >= 0 && kv_better<DESC>(sred[w].v, sred[w].i, best.v, best.i)) best = sred[w];
-  return best;
-}
-
-template <int NV>
-__global__ __launch_bounds__(256) void simota_dynk_reg_kernel(const LossK p) {
-  __shared__ KV sred[4];
-  const int g = blockIdx.x, b = blockIdx.y;
-  if (g >= p.ngt[b]) return;
-  const float* iour = p.iou + ((size_t)b * p.gmax + g) * p.A;
-  const float* costr = p.cost + ((size_t)b * p.gmax + g) * p.A;
-  int32_t* cntr = (int32_t*)p.matched_iou + (size_t)b * p.A;
-  int32_t* gselr = p.matched_gt + (size_t)b * p.A;
-  float vi[NV], vc[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int a = threadIdx.x + 256 * j;
-    vi[j] = a < p.A ? iour[a] : -1.0f;
-    vc[j] = a < p.A ? costr[a] : SIMOTA_INF;
-  }
+// The block-wide rounds, one ordered selection each.  k = max(1, int(sum of the top-10 IoUs among the candidates)), summed
+// in descending order (yolox_head.py:640-643)
+template <int NV, class Row>
+__device__ __forceinline__ int dynk_k_rounds(const Row& iou, int A, KV* sred) {
   float sum = 0.f, lv = 0.f;
   int li = -1;
   for (int r = 0; r < 10; ++r) {
-    const KV s = block_select_reg<true, NV>(vi, p.A, lv, li, -0.5f, INFINITY, sred);
+    const KV s = block_select<true, NV>(iou, A, lv, li, sred);
     if (s.i < 0) break;
     sum += s.v;
     lv = s.v;
     li = s.i;
   }
-  int k = (int)sum;
-  if (k < 1) k = 1;
-  lv = 0.f;
-  li = -1;
+  const int k = (int)sum;
+  return k < 1 ? 1 : k;
+}
+// ... and the k cheapest candidates of gt g are its matches
+template <int NV, class Row>
+__device__ __forceinline__ void dynk_match_rounds(const Row& cost, int A, int k, int g, int32_t* cntr, int32_t* gselr, KV* sred) {
+  float lv = 0.f;
+  int li = -1;
   for (int r = 0; r < k; ++r) {
-    const KV s = block_select_reg<false, NV>(vc, p.A, lv, li, -INFINITY, SIMOTA_INF, sred);
+    const KV s = block_select<false, NV>(cost, A, lv, li, sred);
     if (s.i < 0) break;
     if (threadIdx.x == 0) {   // matching_matrix[g][s.i] = 1: count the anchor's matches, remember one of its gts
       atomicAdd(cntr + s.i, 1);
@@ -410,7 +356,7 @@ __global__ __launch_bounds__(256) void simota_dynk_reg_kernel(const LossK p) {
   }
 }
 
-// Pre-filtered, rank-sorted variant of simota_dynk_reg_kernel.  The ~20 block-wide selection rounds (each a scan of NV
+// Pre-filtered, rank-sorted selection over a register-resident row.  The ~20 block-wide selection rounds (each a scan of NV
 // registers per thread, a six-step shuffle chain and two barriers: ~2.4 us per round with one wave per SIMD) become:
 //  1. per-thread bests; their 10th best (per-wave rank sort of the 64 lane bests -> 4 x 10 entries -> rank sort of those)
 //     bounds the 10th best ELEMENT from below, so every element of the top 10 is at or before it in the total order;
@@ -421,12 +367,6 @@ __global__ __launch_bounds__(256) void simota_dynk_reg_kernel(const LossK p) {
 // Same total order (ties -> smaller index), same summation order: identical results; a list longer than the block (or
 // k > 10) falls back to the block-wide rounds.
 #define DYNK_CAP 256
-// (bitwise | and &: no short-circuit branches inside the rank loops)
-template <bool DESC>
-__device__ __forceinline__ bool kv_valid(float v) {
-  if (DESC) return !((v <= -0.5f) | (v >= INFINITY));
-  return !((v <= -INFINITY) | (v >= SIMOTA_INF));
-}
 // strictly before (v, i) in the total order
 template <bool DESC>
 __device__ __forceinline__ bool kv_before(float ov, int oi, float v, int i) {
@@ -484,7 +424,6 @@ __global__ __launch_bounds__(256) void simota_dynk_pre_kernel(const LossK p) {
   if (tid < 80) s_wtop[tid / 40][tid % 40].i = -1;
   if (tid < 2) { s_cnt[tid] = 0; s_thr[tid].i = -1; }
   __syncthreads();
-  if (p.dbg == 1) return;
   // ---- the bounds: the 10th largest of the IoU bests, the 10th smallest of the cost bests (i < 0: fewer than ten threads hold
   // a valid element - then all valid elements are listed)
   {
@@ -502,7 +441,6 @@ __global__ __launch_bounds__(256) void simota_dynk_pre_kernel(const LossK p) {
     }
   }
   __syncthreads();
-  if (p.dbg == 2) return;
   {
     const KV ti = s_thr[0], tc = s_thr[1];
 #pragma unroll
@@ -521,7 +459,9 @@ __global__ __launch_bounds__(256) void simota_dynk_pre_kernel(const LossK p) {
   }
   __syncthreads();
   const int Mi = s_cnt[0], Mc = s_cnt[1];
-  if (p.dbg == 3) return;
+  const auto row_i = [&](int j, int) { return vi[j]; };
+  const auto row_c = [&](int j, int) { return vc[j]; };
+  int k;
   if (Mi <= DYNK_CAP && Mc <= DYNK_CAP) {
     KV ec;
     ec.v = 0.f;
@@ -543,7 +483,7 @@ __global__ __launch_bounds__(256) void simota_dynk_pre_kernel(const LossK p) {
     float sum = 0.f;
     const int ntop = Mi < 10 ? Mi : 10;
     for (int r = 0; r < ntop; ++r) sum += s_top[r];
-    int k = (int)sum;
+    k = (int)sum;
     if (k < 1) k = 1;
     if (k <= 10) {
       if (rc < k) {   // matching_matrix[g][a] = 1: count the anchor's matches, remember one of its gts
@@ -552,47 +492,14 @@ __global__ __launch_bounds__(256) void simota_dynk_pre_kernel(const LossK p) {
       }
       return;
     }
-    // (k > 10 cannot come out of ten IoUs <= 1; kept exact anyway)
-    float lv = 0.f;
-    int li = -1;
-    for (int r = 0; r < k; ++r) {
-      const KV s = block_select_reg<false, NV>(vc, p.A, lv, li, -INFINITY, SIMOTA_INF, sred);
-      if (s.i < 0) break;
-      if (tid == 0) {
-        atomicAdd(cntr + s.i, 1);
-        atomicMax(gselr + s.i, g);
-      }
-      lv = s.v;
-      li = s.i;
-    }
-    return;
+    // (k > 10 cannot come out of ten IoUs <= 1; kept exact anyway: the block-wide rounds below)
+  } else {
+    k = dynk_k_rounds<NV>(row_i, p.A, sred);   // a list overflowed
   }
-  // ---- a list overflowed: the block-wide rounds
-  float sum = 0.f, lv = 0.f;
-  int li = -1;
-  for (int r = 0; r < 10; ++r) {
-    const KV s = block_select_reg<true, NV>(vi, p.A, lv, li, -0.5f, INFINITY, sred);
-    if (s.i < 0) break;
-    sum += s.v;
-    lv = s.v;
-    li = s.i;
-  }
-  int k = (int)sum;
-  if (k < 1) k = 1;
-  lv = 0.f;
-  li = -1;
-  for (int r = 0; r < k; ++r) {
-    const KV s = block_select_reg<false, NV>(vc, p.A, lv, li, -INFINITY, SIMOTA_INF, sred);
-    if (s.i < 0) break;
-    if (tid == 0) {
-      atomicAdd(cntr + s.i, 1);
-      atomicMax(gselr + s.i, g);
-    }
-    lv = s.v;
-    li = s.i;
-  }
+  dynk_match_rounds<NV>(row_c, p.A, k, g, cntr, gselr, sred);
 }
 
+// any number of anchors (A > 256 * 33: above 8448, e.g. 672 x 672 and larger inputs): the block-wide rounds over the rows in memory
 __global__ __launch_bounds__(256) void simota_dynk_kernel(const LossK p) {
   __shared__ KV sred[4];
   const int g = blockIdx.x, b = blockIdx.y;
@@ -601,30 +508,9 @@ __global__ __launch_bounds__(256) void simota_dynk_kernel(const LossK p) {
   const float* costr = p.cost + ((size_t)b * p.gmax + g) * p.A;
   int32_t* cntr = (int32_t*)p.matched_iou + (size_t)b * p.A;
   int32_t* gselr = p.matched_gt + (size_t)b * p.A;
-  // top-10 IoU among candidates (iou >= 0), summed in descending order
-  float sum = 0.f, lv = 0.f;
-  int li = -1;
-  for (int r = 0; r < 10; ++r) {
-    const KV s = block_select<true>(iour, p.A, lv, li, -0.5f, INFINITY, sred);
-    if (s.i < 0) break;
-    sum += s.v;
-    lv = s.v;
-    li = s.i;
-  }
-  int k = (int)sum;
-  if (k < 1) k = 1;
-  lv = 0.f;
-  li = -1;
-  for (int r = 0; r < k; ++r) {
-    const KV s = block_select<false>(costr, p.A, lv, li, -INFINITY, SIMOTA_INF, sred);
-    if (s.i < 0) break;
-    if (threadIdx.x == 0) {   // matching_matrix[g][s.i] = 1: count the anchor's matches, remember one of its gts
-      atomicAdd(cntr + s.i, 1);
-      atomicMax(gselr + s.i, g);
-    }
-    lv = s.v;
-    li = s.i;
-  }
+  const auto row_i = [&](int, int a) { return iour[a]; };
+  const auto row_c = [&](int, int a) { return costr[a]; };
+  dynk_match_rounds<0>(row_c, p.A, dynk_k_rounds<0>(row_i, p.A, sred), g, cntr, gselr, sred);
 }
 
 // shared decode of one prediction row
@@ -793,7 +679,6 @@ static int loss_fill(const mi_yolox_loss_desc* d, LossK* k) {
   k->iou_weight = d->iou_weight > 0.f ? d->iou_weight : 3.0f;
   k->reg_weight = d->reg_weight > 0.f ? d->reg_weight : 5.0f;
   k->iou_type = d->iou_type;
-  k->dbg = 0;
   MI_REQUIRE(d->iou_type >= 0 && d->iou_type <= 4, "yolox_loss: iou_type %d", d->iou_type);
   MI_REQUIRE(!k->use_l1 || d->partial_l1, "yolox_loss: use_l1 needs partial_l1");
   return MI_OK;
@@ -805,33 +690,19 @@ extern "C" int mi_yolox_loss_fwd(const mi_yolox_loss_desc* d, mi_stream_t st) {
   if (rc) return rc;
   hipStream_t s = (hipStream_t)st;
   const int nb = mi_cdiv(d->A, 256);
-  // MI_SIMOTA_COMPACT=0 (1: compaction only) / MI_SIMOTA_PREFILTER=0: the round-5 forms of the two kernels (read per call: the tests compare
-  // both forms in one process; identical outputs)
-  const char* e1 = getenv("MI_SIMOTA_COMPACT");
-  const char* e2 = getenv("MI_SIMOTA_PREFILTER");
-  int form = e1 ? atoi(e1) : 2;
-  const bool pre = !e2 || atoi(e2) != 0;
-  if (form == 2 && SIMOTA_TERM_FLOATS / (d->ncls + 1) < 16) form = 1;   // (very many classes: the terms of 16 candidates do not fit)
-  const char* e3 = getenv("MI_SIMOTA_DBG");
-  k.dbg = e3 ? atoi(e3) : 0;
   const size_t slab_bytes = d->gmax * 5 * sizeof(float);
-  // (128-anchor blocks - simota_cost_kernel<2, 128> - measured slower: 91.8 vs 83.3 us for the four launches)
-  if (form == 2)
-    hipLaunchKernelGGL(simota_cost_kernel<2>, dim3(nb, d->B), dim3(256), slab_bytes + SIMOTA_TERM_FLOATS * sizeof(float), s, k);
-  else if (form == 1)
-    hipLaunchKernelGGL(simota_cost_kernel<1>, dim3(nb, d->B), dim3(256), slab_bytes, s, k);
-  else
-    hipLaunchKernelGGL(simota_cost_kernel<0>, dim3(nb, d->B), dim3(256), slab_bytes, s, k);
+  // (128-anchor blocks measured slower: 91.8 vs 83.3 us for the four launches)
+  if (SIMOTA_TERM_FLOATS / (d->ncls + 1) >= 16)
+    hipLaunchKernelGGL(simota_cost_kernel<true>, dim3(nb, d->B), dim3(256), slab_bytes + SIMOTA_TERM_FLOATS * sizeof(float), s, k);
+  else   // (very many classes: the terms of 16 candidates do not fit)
+    hipLaunchKernelGGL(simota_cost_kernel<false>, dim3(nb, d->B), dim3(256), slab_bytes, s, k);
   MI_CHECK_LAUNCH("simota_cost");
-  if (d->A <= 256 * 9) {
-    if (pre) hipLaunchKernelGGL(simota_dynk_pre_kernel<9>, dim3(d->gmax, d->B), dim3(256), 0, s, k);
-    else hipLaunchKernelGGL(simota_dynk_reg_kernel<9>, dim3(d->gmax, d->B), dim3(256), 0, s, k);
-  } else if (d->A <= 256 * 33) {
-    if (pre) hipLaunchKernelGGL(simota_dynk_pre_kernel<33>, dim3(d->gmax, d->B), dim3(256), 0, s, k);
-    else hipLaunchKernelGGL(simota_dynk_reg_kernel<33>, dim3(d->gmax, d->B), dim3(256), 0, s, k);
-  } else {
+  if (d->A <= 256 * 9)
+    hipLaunchKernelGGL(simota_dynk_pre_kernel<9>, dim3(d->gmax, d->B), dim3(256), 0, s, k);
+  else if (d->A <= 256 * 33)
+    hipLaunchKernelGGL(simota_dynk_pre_kernel<33>, dim3(d->gmax, d->B), dim3(256), 0, s, k);
+  else
     hipLaunchKernelGGL(simota_dynk_kernel, dim3(d->gmax, d->B), dim3(256), 0, s, k);
-  }
   MI_CHECK_LAUNCH("simota_dynk");
   hipLaunchKernelGGL(simota_resolve_loss_kernel, dim3(nb, d->B), dim3(256), 0, s, k);
   MI_CHECK_LAUNCH("simota_resolve_loss");
