@@ -144,8 +144,9 @@ def test_bottleneck_vd_fwd_bwd(cin, cout, bc, stride, H, W):
 
 @pytest.mark.parametrize("cin,cout,bc,stride,H,W", BLOCK_CASES, ids=BLOCK_IDS)
 def test_bottleneck_vd_as_one_node_equals_the_per_module_composition(cin, cout, bc, stride, H, W, monkeypatch):
-    """_BottleneckVDFn against conv-by-conv autograd nodes (+ the pool's own node and autograd's additions): same kernels and
-    roundings -> identical output and weight gradients, the input gradient within the 4e-3 of the d2 block's test"""
+    """resnet._BottleneckFn (the node the vd block shares with the d2 block) against conv-by-conv autograd nodes (+ the
+    pool's own node and autograd's additions): same kernels and roundings -> identical output and weight
+    gradients, the input gradient within the 4e-3 of the d2 block's test"""
     monkeypatch.setenv("MI_WGRAD_LAYER_GROUP", "0")     # one launch per weight gradient on both sides
     monkeypatch.setenv("MI_RESNET_EPI_FUSE", "0")       # (the node structure is under test)
     blk, _, g = _block_pair(cin, cout, bc, stride)
@@ -158,7 +159,7 @@ def test_bottleneck_vd_as_one_node_equals_the_per_module_composition(cin, cout, 
         blk.zero_grad(set_to_none=True)
         xi = x.clone().requires_grad_(True)
         out = blk(xi)
-        assert (type(out.grad_fn).__name__ == "_BottleneckVDFnBackward") == (flag == "1")
+        assert (type(out.grad_fn).__name__ == "_BottleneckFnBackward") == (flag == "1")
         out.backward(go)
         res.append([out.detach().float(), xi.grad.float()] + [p.grad.float().clone() for p in blk.parameters()])
     for i, (a, b) in enumerate(zip(*res)):

@@ -69,23 +69,6 @@ def _nhwc_view(x):
     return x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
 
 
-class _EwRelu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a):          # a: contiguous bf16
-        y = torch.empty_like(a)
-        L.check(L.lib().mi_ew_bf16(a.data_ptr(), None, y.data_ptr(), a.numel(), 1, L.stream_ptr()), "mi_ew_bf16 relu")
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        (y,) = ctx.saved_tensors
-        g = g.contiguous()
-        out = torch.empty_like(g)
-        L.check(L.lib().mi_ew_bf16(g.data_ptr(), y.data_ptr(), out.data_ptr(), g.numel(), 2, L.stream_ptr()), "mi_ew_bf16 relu'")
-        return out
-
-
 class _EwAddRelu(torch.autograd.Function):
     """relu(a + b): the tail of a bottleneck block"""
 
@@ -103,16 +86,6 @@ class _EwAddRelu(torch.autograd.Function):
         out = torch.empty_like(g)
         L.check(L.lib().mi_ew_bf16(g.data_ptr(), y.data_ptr(), out.data_ptr(), g.numel(), 2, L.stream_ptr()), "mi_ew_bf16 relu'")
         return out, out
-
-
-def _conv_relu_fused():
-    """MI_CONV_RELU_FUSE=0 keeps the ReLU after a bottleneck's conv1 / conv2 as its own pass (A/B switch)"""
-    return os.environ.get("MI_CONV_RELU_FUSE", "1") != "0"
-
-
-def _relu(x):
-    """NCHW (channels_last) bf16 -> same layout"""
-    return _EwRelu.apply(_nhwc_view(x)).permute(0, 3, 1, 2)
 
 
 def _add_relu(a, b):
@@ -169,36 +142,30 @@ def conv_norm_forward(owner, weight, norm, stride, padding, x, relu=False, add_r
     """Conv2d.forward for any (OIHW weight, FrozenBatchNorm2d) pair - modeling/resnet_vd.py keeps them in separate modules
     under timm's names.  owner: the module whose __dict__ keeps the frozen layer's packed image"""
     scale, shift = norm.affine()
-    if add_relu is not None and (not _FOLDED_FN() or (weight.requires_grad and torch.is_grad_enabled())
-                                 or (x.requires_grad and torch.is_grad_enabled())):
-        raise L.MI355Error("Conv2d.forward(add_relu=...): only on the frozen / no-autograd path")
-    if not _FOLDED_FN():
-        w = weight * scale.view(-1, 1, 1, 1)
-        op = torch.ops.mi355.conv2d_relu if relu else torch.ops.mi355.conv2d
-        if not weight.requires_grad:
-            with torch.no_grad():
-                return op(x, w, shift, stride, padding)
-        return op(x, w, shift, stride, padding)
-    train_w = weight.requires_grad and torch.is_grad_enabled()
-    if not train_w and not (x.requires_grad and torch.is_grad_enabled()):
-        g = _ConvGeom(x.shape, weight.shape, stride, padding)
-        with torch.no_grad():
-            if weight.requires_grad:
-                # a TRAINABLE layer run without autograd (evaluation between training steps): packed per call - its
-                # weight may have been updated by a kernel that torch's version counter does not see
-                # (mi_adamw_step_multi, the arena SGD), so no key could tell a stale image from a fresh one
-                wf = g.pack(weight, dgrad=False, scale=scale)[0]
-            else:
-                # a frozen layer under a frozen prefix (FREEZE_AT): its packed image is a constant too.  Keyed on the
-                # identity + write counters of the weight and of the four norm buffers (load_state_dict / .to() change
-                # them), not on the address of `scale`: a recomputed scale may be handed the freed one's address
-                key = (weight.data_ptr(), weight._version, norm.__dict__["_affine"][0])
-                c = owner.__dict__.get("_image")
-                if c is None or c[0] != key:
-                    c = owner.__dict__["_image"] = (key, _same_address(c, g.pack(weight, dgrad=False, scale=scale)[0]))
-                wf = c[1]
-            return _folded_forward(g, x, wf, shift, relu, add_relu)[1]
-    return _FoldedConvFn.apply(x, weight, scale, shift, stride, padding, relu)
+    if torch.is_grad_enabled() and (weight.requires_grad or x.requires_grad):
+        if add_relu is not None:
+            raise L.MI355Error("Conv2d.forward(add_relu=...): only on the frozen / no-autograd path")
+        return _FoldedConvFn.apply(x, weight, scale, shift, stride, padding, relu)
+    g = _ConvGeom(x.shape, weight.shape, stride, padding)
+    with torch.no_grad():
+        pack = lambda: g.pack(weight, dgrad=False, scale=scale)[0]
+        # a TRAINABLE layer run without autograd (evaluation between training steps) is packed per call: its weight may
+        # have been updated by a kernel that torch's version counter does not see (mi_adamw_step_multi, the arena SGD),
+        # so no key could tell a stale image from a fresh one.  A frozen layer (FREEZE_AT prefix) keeps its image
+        wf = pack() if weight.requires_grad else _frozen_image(owner, weight, norm, pack)
+        return _folded_forward(g, x, wf, shift, relu, add_relu)[1]
+
+
+def _frozen_image(owner, weight, norm, pack):
+    """the packed image of a FROZEN layer: a constant, made by pack() once and kept in owner.__dict__.  Keyed on the identity
+    + write counters of the weight and of the four norm buffers (load_state_dict / .to() change them), not on the address
+    of `scale`: a recomputed scale may be handed the freed one's address.  A changed key re-packs INTO the same tensor"""
+    norm.affine()
+    key = (weight.data_ptr(), weight._version, norm.__dict__["_affine"][0])
+    c = owner.__dict__.get("_image")
+    if c is None or c[0] != key:
+        c = owner.__dict__["_image"] = (key, _same_address(c, pack()))
+    return c[1]
 
 
 def _same_address(cached, new):
@@ -208,12 +175,6 @@ def _same_address(cached, new):
         cached[1].copy_(new)
         return cached[1]
     return new
-
-
-def _FOLDED_FN():
-    """MI_RESNET_FOLDED_FN=0: the round-2 form (mi355::conv2d on `weight * scale`; packs in forward AND backward,
-    a bias gradient nobody reads) - A/B switch"""
-    return os.environ.get("MI_RESNET_FOLDED_FN", "1") != "0"
 
 
 def _folded_forward(g, x, wf, shift, relu, add_relu=None):
@@ -278,10 +239,7 @@ class _StemFn(torch.autograd.Function):
     def forward(ctx, s2d, w7, scale, shift):
         N, Hh, Wh, _ = s2d.shape
         Cout, Cin = w7.shape[0], w7.shape[1]
-        w4 = _w7_to_w4(w7 * scale.view(-1, 1, 1, 1))
-        wf = torch.empty(16 * 16 * Cout, dtype=torch.bfloat16, device=s2d.device)
-        L.check(L.lib().mi_pack_conv_weight(w4.contiguous().data_ptr(), Cout, 4 * Cin, 4, 4, wf.data_ptr(), 16, Cout,
-                                            None, 0, 0, L.stream_ptr()), "mi_pack_conv_weight (stem)")
+        wf = _pack_w7(w7 * scale.view(-1, 1, 1, 1))
         a = torch.empty(N, Hh, Wh, Cout, dtype=torch.bfloat16, device=s2d.device)
         _run_conv(_conv_desc(s2d.data_ptr(), 16, N, Hh, Wh, wf, 16, a.data_ptr(), Cout, Hh, Wh, Cout, Cout, _STEM_TAPS,
                              bias=shift.float().contiguous(), flags=L.MI_CONV_RELU),
@@ -306,18 +264,7 @@ class _StemFn(torch.autograd.Function):
                                             L.stream_ptr()), "maxpool bwd")
         dy = torch.empty_like(a)
         L.check(lib.mi_ew_bf16(da.data_ptr(), a.data_ptr(), dy.data_ptr(), a.numel(), 2, L.stream_ptr()), "relu bwd")
-        gw4 = torch.empty(Cout, 4 * Cin, 4, 4, dtype=torch.float32, device=a.device)
-        d = L.mi_wgrad_desc()
-        d.x, d.dy, d.gw = s2d.data_ptr(), dy.data_ptr(), gw4.data_ptr()
-        d.ldx, d.ldy, d.N, d.H, d.W, d.outH, d.outW, d.stride = 16, Cout, N, Hh, Wh, Hh, Wh, 1
-        d.Cin, d.Cout, d.CinPad, d.CoutPad, d.ntaps = 4 * Cin, Cout, 16, Cout, 16
-        for t, (dy_, dx_, _) in enumerate(_STEM_TAPS):
-            d.tap_dy[t], d.tap_dx[t] = dy_, dx_
-        need = lib.mi_conv2d_wgrad_plan(C.byref(d))
-        L.check(need, "mi_conv2d_wgrad_plan (stem)")
-        ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=a.device)
-        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
-        L.check(lib.mi_conv2d_wgrad(C.byref(d), L.stream_ptr()), "mi_conv2d_wgrad (stem)")
+        gw4 = _stem_wgrad(s2d, dy, 4 * Cin, [(dy_, dx_) for dy_, dx_, _ in _STEM_TAPS])
         # [Cout][(px*2+py)*Cin + c][Ay][Ax] -> 8x8 kernel rows R = 2 Ay + py -> drop the zero row / column -> 7x7
         g8 = gw4.view(Cout, 2, 2, Cin, 4, 4).permute(0, 3, 4, 2, 5, 1).reshape(Cout, Cin, 8, 8)
         gw7 = g8[:, :, 1:, 1:] * scale.view(-1, 1, 1, 1)
@@ -328,12 +275,43 @@ class _StemFn(torch.autograd.Function):
 _STEM_TAPS = [(ay - 2, ax - 2, ay * 4 + ax) for ay in range(4) for ax in range(4)]
 
 
+def _stem_wgrad(s2d, dy, cin, taps):
+    """weight gradient of a stride-1 stem convolution over the space-to-depth image: s2d bf16 [N, Hh, Wh, 16] (its first
+    `cin` channels are real), dy bf16 [N, Hh, Wh, Cout], taps [(dy, dx)] (1, 9 or 16 of them) -> fp32 [Cout, cin, len(taps)].
+    The mapping back to the 7x7 / 3x3 OIHW gradient stays with the caller"""
+    N, Hh, Wh, _ = s2d.shape
+    Cout = dy.shape[-1]
+    gw = torch.empty(Cout, cin, len(taps), dtype=torch.float32, device=dy.device)
+    d = L.mi_wgrad_desc()
+    d.x, d.dy, d.gw = s2d.data_ptr(), dy.data_ptr(), gw.data_ptr()
+    d.ldx, d.ldy, d.N, d.H, d.W, d.outH, d.outW, d.stride = 16, Cout, N, Hh, Wh, Hh, Wh, 1
+    d.Cin, d.Cout, d.CinPad, d.CoutPad, d.ntaps = cin, Cout, 16, Cout, len(taps)
+    for t, (dy_, dx_) in enumerate(taps):
+        d.tap_dy[t], d.tap_dx[t] = dy_, dx_
+    need = L.lib().mi_conv2d_wgrad_plan(C.byref(d))
+    L.check(need, "mi_conv2d_wgrad_plan (stem)")
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dy.device)
+    d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().mi_conv2d_wgrad(C.byref(d), L.stream_ptr()), "mi_conv2d_wgrad (stem)")
+    return gw
+
+
 def _w7_to_w4(w7s):
     """7x7 kernel -> 8x8 with a zero first row / column -> [Cout][q = py + 2 px][c] x 4x4 taps (ay, ax in -2..1)"""
     Cout, Cin = w7s.shape[:2]
     w8 = w7s.new_zeros(Cout, Cin, 8, 8)
     w8[:, :, 1:, 1:] = w7s
     return w8.view(Cout, Cin, 4, 2, 4, 2).permute(0, 5, 3, 1, 2, 4).reshape(Cout, 4 * Cin, 4, 4)   # ch = (px*2+py)*Cin+c
+
+
+def _pack_w7(w7s):
+    """the (scaled) 7x7 stem weight -> the forward image of its 16-tap form"""
+    Cout, Cin = w7s.shape[:2]
+    w4 = _w7_to_w4(w7s).contiguous()
+    wf = torch.empty(16 * 16 * Cout, dtype=torch.bfloat16, device=w7s.device)
+    L.check(L.lib().mi_pack_conv_weight(w4.data_ptr(), Cout, 4 * Cin, 4, 4, wf.data_ptr(), 16, Cout, None, 0, 0, L.stream_ptr()),
+            "mi_pack_conv_weight (stem)")
+    return wf
 
 
 class BasicStem(nn.Module):
@@ -361,20 +339,12 @@ class BasicStem(nn.Module):
         with torch.no_grad():       # frozen stem (FREEZE_AT >= 1): the packed image is a constant, kept across steps
             Cout = w7.shape[0]
             # (a TRAINABLE stem run without autograd is packed per call: kernels that update weights bypass torch's
-            #  version counter, see Conv2d.forward)
-            key = None if w7.requires_grad else (w7.data_ptr(), w7._version, self.conv1.norm.__dict__["_affine"][0])
-            c = self.__dict__.get("_image")
-            if key is None or c is None or c[0] != key:
-                w4 = _w7_to_w4(w7 * scale.view(-1, 1, 1, 1)).contiguous()
-                wf = torch.empty(16 * 16 * Cout, dtype=torch.bfloat16, device=x.device)
-                L.check(L.lib().mi_pack_conv_weight(w4.data_ptr(), Cout, 4 * Cin, 4, 4, wf.data_ptr(), 16, Cout, None, 0, 0,
-                                                    L.stream_ptr()), "mi_pack_conv_weight (stem)")
-                c = (key, _same_address(c, wf) if key is not None else wf)
-                if key is not None:
-                    self.__dict__["_image"] = c
+            #  version counter, see conv_norm_forward)
+            pack = lambda: _pack_w7(w7 * scale.view(-1, 1, 1, 1))
+            wf = pack() if w7.requires_grad else _frozen_image(self, w7, self.conv1.norm, pack)
             Hh, Wh = He // 2, We // 2
             a = torch.empty(N, Hh, Wh, Cout, dtype=torch.bfloat16, device=x.device)
-            _run_conv(_conv_desc(s2d.data_ptr(), 16, N, Hh, Wh, c[1], 16, a.data_ptr(), Cout, Hh, Wh, Cout, Cout, _STEM_TAPS,
+            _run_conv(_conv_desc(s2d.data_ptr(), 16, N, Hh, Wh, wf, 16, a.data_ptr(), Cout, Hh, Wh, Cout, Cout, _STEM_TAPS,
                                  bias=shift, flags=L.MI_CONV_RELU), "mi_conv2d (7x7 stem as 4x4 over space-to-depth)")
             out = torch.empty(N, (Hh + 1) // 2, (Wh + 1) // 2, Cout, dtype=torch.bfloat16, device=x.device)
             L.check(L.lib().mi_maxpool3x3s2_fwd(a.data_ptr(), Cout, out.data_ptr(), Cout, N, Hh, Wh, Cout, L.stream_ptr()),
@@ -384,7 +354,7 @@ class BasicStem(nn.Module):
 
 def _BLOCK_FN():
     """MI_RESNET_BLOCK_FN=0: every convolution of a trainable bottleneck block is its own autograd node again (A/B switch)"""
-    return _FOLDED_FN() and os.environ.get("MI_RESNET_BLOCK_FN", "1") != "0"
+    return os.environ.get("MI_RESNET_BLOCK_FN", "1") != "0"
 
 
 def _EPI_FUSE():
@@ -429,20 +399,41 @@ def _MASK_FUSE():
     return os.environ.get("MI_RESNET_MASK_FUSE", "1") == "1"
 
 
+def avgpool2x2(xh):
+    """bf16 NHWC (dense or a channel slice) -> AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) of it, dense"""
+    N, H, W, Cc = xh.shape
+    y = torch.empty(N, (H + 1) // 2, (W + 1) // 2, Cc, dtype=torch.bfloat16, device=xh.device)
+    L.check(L.lib().mi_avgpool2x2s2_fwd(xh.data_ptr(), _ld(xh), y.data_ptr(), Cc, N, H, W, Cc, L.stream_ptr()), "mi_avgpool2x2s2_fwd")
+    return y
+
+
+def avgpool2x2_bwd(dyh, dxh, accumulate=False, mask=None):
+    """dxh [N,H,W,C] (+)= dyh[iy / 2][ix / 2] / count, zeroed where mask <= 0 (mask: bf16 NHWC of dxh's shape)"""
+    N, H, W, Cc = dxh.shape
+    L.check(L.lib().mi_avgpool2x2s2_bwd(dyh.data_ptr(), _ld(dyh), dxh.data_ptr(), _ld(dxh), L.ptr(mask), _ld(mask) if mask is not None else 0,
+                                        1 if accumulate else 0, N, H, W, Cc, L.stream_ptr()), "mi_avgpool2x2s2_bwd")
+    return dxh
+
+
 class _BottleneckFn(torch.autograd.Function):
-    """A trainable BottleneckBlock (detectron2 resnet.py BottleneckBlock: conv1 1x1 - conv2 3x3 - conv3 1x1, FrozenBN folded,
-    + shortcut, ReLU) as ONE autograd node.  What the per-convolution nodes cannot do: the block input's gradient is the
-    sum of two paths - autograd materialised both and added them (a three-tensor pass over the block's largest map, and a
-    full zero fill under the stride-2 shortcut's data gradient, which writes only the even pixels); here the second path
-    ACCUMULATES into the first in the convolution's epilogue (MI_CONV_ACCUM): identity blocks add conv1's data gradient
-    into the (masked) output gradient, shortcut blocks add the shortcut's data gradient into conv1's.  Same kernels, same
-    roundings as the separate nodes (bf16 + bf16 -> bf16)."""
+    """A trainable bottleneck (conv1 1x1 - conv2 3x3 of stride s2 - conv3 1x1, FrozenBN folded, + shortcut, ReLU) as ONE
+    autograd node: detectron2's BottleneckBlock and the ResNet-vd block (modeling/resnet_vd.py).  The shortcut is
+      ssc 0:               the block input itself (identity block);
+      ssc s, not pooled:   a 1x1 convolution of stride s on the input (d2: s = the block's stride; vd layer1.0: s = 1);
+      ssc 1, pooled:       a 1x1 stride-1 convolution on xp = avgpool2x2(input) (vd, stride-2 blocks).
+    What the per-convolution nodes cannot do: the block input's gradient is the sum of two paths - autograd materialised both
+    and added them (a three-tensor pass over the block's largest map, and a full zero fill under the stride-2 shortcut's data
+    gradient, which writes only the even pixels); here the second path ACCUMULATES into the first in the convolution's epilogue
+    (MI_CONV_ACCUM): identity blocks add conv1's data gradient into the (masked) output gradient, shortcut blocks add the
+    shortcut's data gradient into conv1's.  The pooled shortcut's data gradient is a quarter-size map that
+    mi_avgpool2x2s2_bwd adds into conv1's - a pass over every pixel of the block input, so the input's ReLU mask is taken there
+    (and noted for the previous block) for stride-2 blocks too, which the strided convolution's accumulate, visiting only the
+    even pixels, cannot do.  Same kernels, same roundings as the separate nodes (bf16 + bf16 -> bf16)."""
 
     @staticmethod
-    def forward(ctx, x, s2, ssc, in_relu, *rest):
+    def forward(ctx, x, s2, ssc, pooled, in_relu, *rest):
         n = 4 if ssc else 3
         ws, aff = rest[:n], rest[n:]
-        ctx.in_relu = bool(in_relu)
         scales, shifts = aff[0::2], aff[1::2]
         need_dx = x.requires_grad
         N, Cin, H, W = x.shape
@@ -450,11 +441,14 @@ class _BottleneckFn(torch.autograd.Function):
         g1 = _ConvGeom((N, Cin, H, W), ws[0].shape, 1, 0)
         g2 = _ConvGeom((N, bc, H, W), ws[1].shape, s2, 1)
         g3 = _ConvGeom((N, bc, g2.Ho, g2.Wo), ws[2].shape, 1, 0)
-        gs = _ConvGeom((N, Cin, H, W), ws[3].shape, ssc, 0) if ssc else None
+        Hp, Wp = ((H + 1) // 2, (W + 1) // 2) if pooled else (H, W)
+        gs = _ConvGeom((N, Cin, Hp, Wp), ws[3].shape, ssc, 0) if ssc else None
         geoms = [g1, g2, g3] + ([gs] if ssc else [])
         for g in geoms:
             if g.CinP != g.Cin or g.CoutP != g.Cout:
                 raise L.MI355Error("ResNet bottleneck: channel counts must be multiples of 32")
+        if (ssc and (gs.Ho, gs.Wo) != (g2.Ho, g2.Wo)) or (not ssc and (s2 != 1 or Cin != ws[2].shape[0])):
+            raise L.MI355Error("ResNet bottleneck: the shortcut's map does not match conv3's")
         imgs = [g.pack(w, dgrad=(need_dx or i in (1, 2)), scale=sc)
                 for i, (g, w, sc) in enumerate(zip(geoms, ws, scales))]
         dev = x.device
@@ -466,7 +460,8 @@ class _BottleneckFn(torch.autograd.Function):
             return y
         a1 = run(g1, xh, 0, True)
         a2 = run(g2, a1, 1, True)
-        sc = run(gs, xh, 3, False) if ssc else xh
+        xp = avgpool2x2(xh) if pooled else None
+        sc = run(gs, xp if pooled else xh, 3, False) if ssc else xh
         ctx.epi = _EPI_FUSE()
         if ctx.epi:
             y = run(g3, a2, 2, False, add_relu=sc)            # relu(bf16(conv3 + shift) + shortcut) in conv3's epilogue
@@ -474,64 +469,88 @@ class _BottleneckFn(torch.autograd.Function):
             o = run(g3, a2, 2, False)
             y = torch.empty_like(o)
             L.check(L.lib().mi_ew_bf16(o.data_ptr(), sc.data_ptr(), y.data_ptr(), o.numel(), 7, L.stream_ptr()), "mi_ew_bf16 add+relu")
-        ctx.geoms, ctx.has_sc = geoms, bool(ssc)
+        ctx.geoms, ctx.pooled, ctx.in_relu = geoms, bool(pooled), bool(in_relu)
         ctx.params = ws
-        ctx.save_for_backward(xh, a1, a2, y, *[im[1] for im in imgs], *scales)
+        ctx.save_for_backward(xh, a1, a2, y, xp, *[im[1] for im in imgs], *scales)
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
-        n = 4 if ctx.has_sc else 3
-        xh, a1, a2, y = ctx.saved_tensors[:4]
-        wds, scales = ctx.saved_tensors[4:4 + n], ctx.saved_tensors[4 + n:]
+        n = len(ctx.geoms)
+        xh, a1, a2, y, xp = ctx.saved_tensors[:5]
+        wds, scales = ctx.saved_tensors[5:5 + n], ctx.saved_tensors[5 + n:]
         g1, g2, g3 = ctx.geoms[:3]
-        gs = ctx.geoms[3] if ctx.has_sc else None
-        dev = xh.device
+        gs = ctx.geoms[3] if n == 4 else None
         gyh = _nhwc(gy)
         if _premask_take(gyh):
-            gm = gyh                        # the next block's backward masked it in its last epilogue (and owns no other use of it)
+            gm = gyh                        # the next block's backward masked it in its last pass (and owns no other use of it)
         else:
-            gm = torch.empty_like(gyh)      # (a fresh tensor: identity blocks accumulate the input gradient into it)
-            L.check(L.lib().mi_ew_bf16(gyh.data_ptr(), y.data_ptr(), gm.data_ptr(), gm.numel(), 2, L.stream_ptr()), "mi_ew_bf16 relu'")
+            gm = _relu_mask(gyh, y)         # (a fresh tensor: identity blocks accumulate the input gradient into it)
         gws = [None] * n
         # the block's three or four weight gradients as ONE grouped launch (ops.WgradBatch), issued below - before the input
         # gradient is accumulated INTO gm, which two of the jobs read
         df = wgrad_can_defer(*ctx.params)
-        gws[2] = g3.wgrad_scaled(a2, gm, scales[2], defer=df, owner=ctx.params[2] if df else None)
+        owner = lambda i: ctx.params[i] if df else None
+        gws[2] = g3.wgrad_scaled(a2, gm, scales[2], defer=df, owner=owner(2))
         da2 = torch.empty_like(a2)
         if ctx.epi:
             g3.dgrad(gm, wds[2], da2, relu_mask=a2)
         else:
             g3.dgrad(gm, wds[2], da2)
             da2 = _relu_mask(da2, a2)
-        gws[1] = g2.wgrad_scaled(a1, da2, scales[1], defer=df, owner=ctx.params[1] if df else None)
+        gws[1] = g2.wgrad_scaled(a1, da2, scales[1], defer=df, owner=owner(1))
         da1 = torch.empty_like(a1)
         if ctx.epi:
             g2.dgrad(da2, wds[1], da1, relu_mask=a1)
         else:
             g2.dgrad(da2, wds[1], da1)
             da1 = _relu_mask(da1, a1)
-        gws[0] = g1.wgrad_scaled(xh, da1, scales[0], defer=df, owner=ctx.params[0] if df else None)
+        gws[0] = g1.wgrad_scaled(xh, da1, scales[0], defer=df, owner=owner(0))
         if gs is not None:
-            gws[3] = gs.wgrad_scaled(xh, gm, scales[3], defer=df, owner=ctx.params[3] if df else None)
+            gws[3] = gs.wgrad_scaled(xp if ctx.pooled else xh, gm, scales[3], defer=df, owner=owner(3))
         if df:
             WgradBatch.flush()
         dx = None
         if ctx.needs_input_grad[0]:
-            # the block input is a ReLU output (ResNet sets in_relu): its mask goes into the LAST data gradient's epilogue
-            # (not for the stride-2 shortcut, whose accumulate visits only the even pixels)
-            fuse = ctx.in_relu and ctx.epi and _MASK_FUSE() and (gs is None or gs.s == 1)
+            # the block input is a ReLU output (the backbones set input_is_relu): its mask goes into the LAST pass over its
+            # gradient - the pool's backward, or the last data gradient's epilogue (not the stride-2 shortcut's, whose
+            # accumulate visits only the even pixels)
+            fuse = ctx.in_relu and _MASK_FUSE() and (ctx.pooled or (ctx.epi and (gs is None or gs.s == 1)))
+            mask = xh if fuse else None
             if gs is None:
                 dxh = gm
-                g1.dgrad(da1, wds[0], dxh, accum=True, relu_mask=xh if fuse else None)
+                g1.dgrad(da1, wds[0], dxh, accum=True, relu_mask=mask)
             else:
                 dxh = torch.empty_like(xh)
                 g1.dgrad(da1, wds[0], dxh)
-                gs.dgrad(gm, wds[3], dxh, accum=True, relu_mask=xh if fuse else None)
+                if ctx.pooled:
+                    dp = torch.empty_like(xp)
+                    gs.dgrad(gm, wds[3], dp)
+                    avgpool2x2_bwd(dp, dxh, accumulate=True, mask=mask)
+                else:
+                    gs.dgrad(gm, wds[3], dxh, accum=True, relu_mask=mask)
             if fuse:
                 _premask_note(dxh)
             dx = dxh.permute(0, 3, 1, 2)
-        return (dx, None, None, None, *gws, *([None] * (2 * n)))
+        return (dx, None, None, None, None, *gws, *([None] * (2 * n)))
+
+
+def _bottleneck_eager(x, convs, w3, shortcut):
+    """A bottleneck as per-convolution launches / autograd nodes: conv1 + ReLU, conv2 + ReLU, shortcut(x), conv3 + shortcut
+    + ReLU.  convs: conv1 .. conv3 as callables (input, relu=False, add_relu=None) - detectron2-shaped blocks pass their
+    Conv2d MODULES, whose forward hooks the tests use to read every convolution's output; w3: conv3's weight"""
+    out = convs[1](convs[0](x, relu=True), relu=True)
+    return _conv3_add_relu(convs[2], w3, out, shortcut(x))
+
+
+def _conv3_add_relu(conv3, w3, out, sc):
+    """relu(conv3(out) + sc).  Without autograd (a frozen block under FREEZE_AT, inference) the add + ReLU run in conv3's
+    epilogue, as _BottleneckFn does for the trainable blocks - the separate pass was a read-read-write of the block's
+    largest map (3 x 73 us per DETR-R50 step for res2 at 800 x 1333)"""
+    autograd = torch.is_grad_enabled() and (out.requires_grad or sc.requires_grad or w3.requires_grad)
+    if not autograd and _EPI_FUSE() and w3.shape[0] % 32 == 0:
+        return conv3(out, add_relu=sc)
+    return _add_relu(conv3(out), sc)
 
 
 class BottleneckBlock(nn.Module):
@@ -548,21 +567,9 @@ class BottleneckBlock(nn.Module):
         convs = [self.conv1, self.conv2, self.conv3] + ([self.shortcut] if self.shortcut is not None else [])
         if (_BLOCK_FN() and torch.is_grad_enabled() and all(c.weight.requires_grad for c in convs) and self.conv1.stride == 1):
             aff = [t for c in convs for t in c.norm.affine()]
-            return _BottleneckFn.apply(x, self.conv2.stride, self.shortcut.stride if self.shortcut is not None else 0,
+            return _BottleneckFn.apply(x, self.conv2.stride, self.shortcut.stride if self.shortcut is not None else 0, False,
                                        getattr(self, "input_is_relu", False), *[c.weight for c in convs], *aff)
-        if _conv_relu_fused():
-            out = self.conv2(self.conv1(x, relu=True), relu=True)
-        else:
-            out = _relu(self.conv2(_relu(self.conv1(x))))
-        sc = self.shortcut(x) if self.shortcut is not None else x
-        no_grad_path = not (torch.is_grad_enabled() and (x.requires_grad or any(c.weight.requires_grad for c in convs)))
-        if no_grad_path and _EPI_FUSE() and _FOLDED_FN() and self.conv3.weight.shape[0] % 32 == 0:
-            # a frozen block (FREEZE_AT prefix) / inference: the residual add + ReLU in conv3's epilogue, as _BottleneckFn
-            # does for the trainable blocks - the separate pass was a read-read-write of the block's largest map
-            # (3 x 73 us per DETR-R50 step for res2 at 800 x 1333)
-            return self.conv3(out, add_relu=sc)
-        out = self.conv3(out)
-        return _add_relu(out, sc)
+        return _bottleneck_eager(x, convs[:3], self.conv3.weight, self.shortcut if self.shortcut is not None else (lambda t: t))
 
 
 def _DEFORM_KEEP_COL():
@@ -697,14 +704,8 @@ class DeformConv(nn.Module):
         # no autograd (evaluation, a frozen stage): nothing saved; a frozen layer's packed image is a constant (Conv2d.forward)
         with torch.no_grad():
             g = _deform_geom(x.shape, weight.shape, self.stride)
-            if weight.requires_grad:
-                wf = g.pack(_tap_major(weight), dgrad=False, scale=scale)[0]
-            else:
-                key = (weight.data_ptr(), weight._version, self.norm.__dict__["_affine"][0])
-                c = self.__dict__.get("_image")
-                if c is None or c[0] != key:
-                    c = self.__dict__["_image"] = (key, _same_address(c, g.pack(_tap_major(weight), dgrad=False, scale=scale)[0]))
-                wf = c[1]
+            pack = lambda: g.pack(_tap_major(weight), dgrad=False, scale=scale)[0]
+            wf = pack() if weight.requires_grad else _frozen_image(self, weight, self.norm, pack)
             xh = _nhwc_v(x)
             off, ldoff = _offset_operand(offset, g.N, g.H, g.W)
             col = _deform_cols(xh, off, ldoff, g.H, g.W, self.stride)
@@ -738,10 +739,7 @@ class DeformBottleneckBlock(nn.Module):
         offset = torch.ops.mi355.conv2d(out, po.weight, po.bias, po.stride[0], 1)
         out = self.conv2(out, offset, relu=True, x_is_relu=True)
         sc = self.shortcut(x) if self.shortcut is not None else x
-        no_grad_path = not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
-        if no_grad_path and _EPI_FUSE() and _FOLDED_FN():
-            return self.conv3(out, add_relu=sc)
-        return _add_relu(self.conv3(out), sc)
+        return _conv3_add_relu(self.conv3, self.conv3.weight, out, sc)
 
 
 class ResNet(Backbone):

@@ -23,32 +23,16 @@ weight gradients):
     and, as it writes every pixel, takes the block input's ReLU mask there as well.
 MODEL.BACKBONE.FREEZE_AT is not read (the reference's builder does not): everything trains.
 """
-import ctypes as C
+import functools
 
 import torch
 from torch import nn
 
 from .. import _lib as L
 from ..d2shim import BACKBONE_REGISTRY, Backbone, ShapeSpec
-from ..ops import WgradBatch, _ConvGeom, _conv_desc, _ld, _nhwc, _run_conv, wgrad_can_defer
-from .resnet import (FrozenBatchNorm2d, _BLOCK_FN, _EPI_FUSE, _FOLDED_FN, _MASK_FUSE, _MaxPool, _add_relu, _conv_relu_fused,
-                     _premask_note, _premask_take, _relu, _relu_mask, _same_address, conv_norm_forward)
-
-
-def avgpool2x2(xh):
-    """bf16 NHWC (dense or a channel slice) -> AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) of it, dense"""
-    N, H, W, Cc = xh.shape
-    y = torch.empty(N, (H + 1) // 2, (W + 1) // 2, Cc, dtype=torch.bfloat16, device=xh.device)
-    L.check(L.lib().mi_avgpool2x2s2_fwd(xh.data_ptr(), _ld(xh), y.data_ptr(), Cc, N, H, W, Cc, L.stream_ptr()), "mi_avgpool2x2s2_fwd")
-    return y
-
-
-def avgpool2x2_bwd(dyh, dxh, accumulate=False, mask=None):
-    """dxh [N,H,W,C] (+)= dyh[iy / 2][ix / 2] / count, zeroed where mask <= 0 (mask: bf16 NHWC of dxh's shape)"""
-    N, H, W, Cc = dxh.shape
-    L.check(L.lib().mi_avgpool2x2s2_bwd(dyh.data_ptr(), _ld(dyh), dxh.data_ptr(), _ld(dxh), L.ptr(mask), _ld(mask) if mask is not None else 0,
-                                        1 if accumulate else 0, N, H, W, Cc, L.stream_ptr()), "mi_avgpool2x2s2_bwd")
-    return dxh
+from ..ops import _conv_desc, _nhwc, _run_conv
+from .resnet import (FrozenBatchNorm2d, _BLOCK_FN, _BottleneckFn, _MaxPool, _bottleneck_eager, _frozen_image, _relu_mask,
+                     _stem_wgrad, avgpool2x2, avgpool2x2_bwd, conv_norm_forward)
 
 
 class _AvgPoolFn(torch.autograd.Function):
@@ -120,21 +104,8 @@ class _Stem0Fn(torch.autograd.Function):
     def backward(ctx, g):
         s2d, a, scale = ctx.saved_tensors
         Cout, Cin = ctx.shape
-        N, Hh, Wh, _ = s2d.shape
-        lib = L.lib()
         dy = _relu_mask(g.contiguous(), a)
-        gw9 = torch.empty(Cout, 4 * Cin, 3, 3, dtype=torch.float32, device=a.device)
-        d = L.mi_wgrad_desc()
-        d.x, d.dy, d.gw = s2d.data_ptr(), dy.data_ptr(), gw9.data_ptr()
-        d.ldx, d.ldy, d.N, d.H, d.W, d.outH, d.outW, d.stride = 16, Cout, N, Hh, Wh, Hh, Wh, 1
-        d.Cin, d.Cout, d.CinPad, d.CoutPad, d.ntaps = 4 * Cin, Cout, 16, Cout, 9
-        for t in range(9):
-            d.tap_dy[t], d.tap_dx[t] = t // 3 - 1, t % 3 - 1
-        need = lib.mi_conv2d_wgrad_plan(C.byref(d))
-        L.check(need, "mi_conv2d_wgrad_plan (deep stem)")
-        ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=a.device)
-        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
-        L.check(lib.mi_conv2d_wgrad(C.byref(d), L.stream_ptr()), "mi_conv2d_wgrad (deep stem)")
+        gw9 = _stem_wgrad(s2d, dy, 4 * Cin, [(t // 3 - 1, t % 3 - 1) for t in range(9)]).view(Cout, 4 * Cin, 3, 3)
         # [Cout][(px*2+py)*Cin + c][Ay][Ax] (taps -1, 0 of the nine) -> 4x4 kernel rows R = 2 Ay + py -> drop the zero row / column
         g4 = gw9[:, :, :2, :2].reshape(Cout, 2, 2, Cin, 2, 2).permute(0, 3, 4, 2, 5, 1).reshape(Cout, Cin, 4, 4)
         return None, g4[:, :, 1:, 1:] * scale.view(-1, 1, 1, 1), None, None
@@ -174,134 +145,12 @@ class BottleneckVD(nn.Module):
         pooled = self.downsample is not None and isinstance(self.downsample[0], AvgPool2x2)
         if _BLOCK_FN() and torch.is_grad_enabled() and all(c.weight.requires_grad for c, _ in pairs):
             aff = [t for _, n in pairs for t in n.affine()]
-            return _BottleneckVDFn.apply(x, self.stride, len(pairs) == 4, pooled, getattr(self, "input_is_relu", False),
-                                         *[c.weight for c, _ in pairs], *aff)
-
-        def conv(i, inp, stride=1, **kw):
-            c, n = pairs[i]
-            return conv_norm_forward(c, c.weight, n, stride, (c.weight.shape[-1] - 1) // 2, inp, **kw)
-        if _conv_relu_fused():
-            out = conv(1, conv(0, x, relu=True), self.stride, relu=True)
-        else:
-            out = _relu(conv(1, _relu(conv(0, x)), self.stride))
-        sc = x
-        if self.downsample is not None:
-            sc = conv(3, self.downsample[0](x))
-        no_grad_path = not (torch.is_grad_enabled() and (x.requires_grad or any(c.weight.requires_grad for c, _ in pairs)))
-        if no_grad_path and _EPI_FUSE() and _FOLDED_FN() and self.conv3.weight.shape[0] % 32 == 0:
-            return conv(2, out, add_relu=sc)       # inference: the residual add + ReLU in conv3's epilogue
-        return _add_relu(conv(2, out), sc)
-
-
-class _BottleneckVDFn(torch.autograd.Function):
-    """A trainable BottleneckVD as ONE autograd node, in the manner of resnet._BottleneckFn (same kernels, same roundings
-    as the per-module composition).  What differs is the projection shortcut: a 1x1 stride-1 convolution on the 2x2 average
-    of the block input.  Its weight gradient reads the saved pooled map and joins the block's grouped launch; its data
-    gradient is a quarter-size map that mi_avgpool2x2s2_bwd adds into conv1's data gradient - a pass over every pixel of the
-    block input, so the input's ReLU mask is taken there (and noted for the previous block) for stride-2 blocks too, which
-    the d2 block's strided shortcut cannot do."""
-
-    @staticmethod
-    def forward(ctx, x, s2, proj, pooled, in_relu, *rest):
-        n = 4 if proj else 3
-        ws, aff = rest[:n], rest[n:]
-        ctx.in_relu = bool(in_relu)
-        scales, shifts = aff[0::2], aff[1::2]
-        need_dx = x.requires_grad
-        N, Cin, H, W = x.shape
-        bc = ws[0].shape[0]
-        g1 = _ConvGeom((N, Cin, H, W), ws[0].shape, 1, 0)
-        g2 = _ConvGeom((N, bc, H, W), ws[1].shape, s2, 1)
-        g3 = _ConvGeom((N, bc, g2.Ho, g2.Wo), ws[2].shape, 1, 0)
-        Hp, Wp = ((H + 1) // 2, (W + 1) // 2) if pooled else (H, W)
-        gs = _ConvGeom((N, Cin, Hp, Wp), ws[3].shape, 1, 0) if proj else None
-        geoms = [g1, g2, g3] + ([gs] if proj else [])
-        for g in geoms:
-            if g.CinP != g.Cin or g.CoutP != g.Cout:
-                raise L.MI355Error("ResNet-vd bottleneck: channel counts must be multiples of 32")
-        if (proj and (gs.Ho, gs.Wo) != (g2.Ho, g2.Wo)) or (not proj and (s2 != 1 or Cin != ws[2].shape[0])):
-            raise L.MI355Error("ResNet-vd bottleneck: the shortcut's map does not match conv3's")
-        imgs = [g.pack(w, dgrad=(need_dx or i in (1, 2)), scale=sc)
-                for i, (g, w, sc) in enumerate(zip(geoms, ws, scales))]
-        dev = x.device
-        xh = _nhwc(x)
-
-        def run(g, inp, i, relu, add_relu=None):
-            y = torch.empty(g.N, g.Ho, g.Wo, g.CoutP, dtype=torch.bfloat16, device=dev)
-            g.fwd(inp, imgs[i][0], y, bias=shifts[i], relu=relu, add_relu=add_relu)
-            return y
-        a1 = run(g1, xh, 0, True)
-        a2 = run(g2, a1, 1, True)
-        xp = avgpool2x2(xh) if pooled else xh
-        sc = run(gs, xp, 3, False) if proj else xh
-        ctx.epi = _EPI_FUSE()
-        if ctx.epi:
-            y = run(g3, a2, 2, False, add_relu=sc)            # relu(bf16(conv3 + shift) + shortcut) in conv3's epilogue
-        else:
-            o = run(g3, a2, 2, False)
-            y = torch.empty_like(o)
-            L.check(L.lib().mi_ew_bf16(o.data_ptr(), sc.data_ptr(), y.data_ptr(), o.numel(), 7, L.stream_ptr()), "mi_ew_bf16 add+relu")
-        ctx.geoms, ctx.proj, ctx.pooled = geoms, bool(proj), bool(pooled)
-        ctx.params = ws
-        ctx.save_for_backward(xh, a1, a2, y, xp if pooled else None, *[im[1] for im in imgs], *scales)
-        return y.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, gy):
-        n = 4 if ctx.proj else 3
-        xh, a1, a2, y, xp = ctx.saved_tensors[:5]
-        wds, scales = ctx.saved_tensors[5:5 + n], ctx.saved_tensors[5 + n:]
-        g1, g2, g3 = ctx.geoms[:3]
-        gs = ctx.geoms[3] if ctx.proj else None
-        gyh = _nhwc(gy)
-        if _premask_take(gyh):
-            gm = gyh                        # the next block's backward masked it in its last pass (and owns no other use of it)
-        else:
-            gm = _relu_mask(gyh, y)         # (a fresh tensor: identity blocks accumulate the input gradient into it)
-        gws = [None] * n
-        # the block's three or four weight gradients as ONE grouped launch (ops.WgradBatch), issued below - before the input
-        # gradient is accumulated INTO gm, which two of the jobs read
-        df = wgrad_can_defer(*ctx.params)
-        gws[2] = g3.wgrad_scaled(a2, gm, scales[2], defer=df, owner=ctx.params[2] if df else None)
-        da2 = torch.empty_like(a2)
-        if ctx.epi:
-            g3.dgrad(gm, wds[2], da2, relu_mask=a2)
-        else:
-            g3.dgrad(gm, wds[2], da2)
-            da2 = _relu_mask(da2, a2)
-        gws[1] = g2.wgrad_scaled(a1, da2, scales[1], defer=df, owner=ctx.params[1] if df else None)
-        da1 = torch.empty_like(a1)
-        if ctx.epi:
-            g2.dgrad(da2, wds[1], da1, relu_mask=a1)
-        else:
-            g2.dgrad(da2, wds[1], da1)
-            da1 = _relu_mask(da1, a1)
-        gws[0] = g1.wgrad_scaled(xh, da1, scales[0], defer=df, owner=ctx.params[0] if df else None)
-        if gs is not None:
-            gws[3] = gs.wgrad_scaled(xp if ctx.pooled else xh, gm, scales[3], defer=df, owner=ctx.params[3] if df else None)
-        if df:
-            WgradBatch.flush()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            # the block input is a ReLU output (ResNetVD sets input_is_relu): its mask goes into the LAST pass over its gradient
-            mask = ctx.in_relu and _MASK_FUSE()
-            fuse = mask and (ctx.epi or ctx.pooled)
-            if gs is None:
-                dxh = gm
-                g1.dgrad(da1, wds[0], dxh, accum=True, relu_mask=xh if fuse else None)
-            else:
-                dxh = torch.empty_like(xh)
-                g1.dgrad(da1, wds[0], dxh)
-                if ctx.pooled:
-                    dp = torch.empty_like(xp)
-                    gs.dgrad(gm, wds[3], dp)
-                    avgpool2x2_bwd(dp, dxh, accumulate=True, mask=xh if fuse else None)
-                else:
-                    gs.dgrad(gm, wds[3], dxh, accum=True, relu_mask=xh if fuse else None)
-            if fuse:
-                _premask_note(dxh)
-            dx = dxh.permute(0, 3, 1, 2)
-        return (dx, None, None, None, None, *gws, *([None] * (2 * n)))
+            return _BottleneckFn.apply(x, self.stride, int(len(pairs) == 4), pooled, getattr(self, "input_is_relu", False),
+                                       *[c.weight for c, _ in pairs], *aff)
+        convs = [functools.partial(conv_norm_forward, c, c.weight, n, stride, (c.weight.shape[-1] - 1) // 2)
+                 for (c, n), stride in zip(pairs, (1, self.stride, 1, 1))]
+        shortcut = (lambda t: t) if self.downsample is None else (lambda t: convs[3](self.downsample[0](t)))
+        return _bottleneck_eager(x, convs[:3], self.conv3.weight, shortcut)
 
 
 def _downsample_avg(cin, cout, stride):
@@ -375,14 +224,9 @@ class ResNetVD(Backbone):
             with torch.no_grad():
                 # (a TRAINABLE stem run without autograd is packed per call: kernels that update weights bypass torch's
                 #  version counter, see resnet.conv_norm_forward; a frozen one keeps its image)
-                key = None if w0.requires_grad else (w0.data_ptr(), w0._version, c[1].__dict__["_affine"][0])
-                img = c[0].__dict__.get("_image")
-                if key is None or img is None or img[0] != key:
-                    wf = _pack_stem(w0 * scale.view(-1, 1, 1, 1))
-                    img = (key, _same_address(img, wf) if key is not None else wf)
-                    if key is not None:
-                        c[0].__dict__["_image"] = img
-                a = _stem_conv(s2d, img[1], shift, w0.shape[0])
+                pack = lambda: _pack_stem(w0 * scale.view(-1, 1, 1, 1))
+                wf = pack() if w0.requires_grad else _frozen_image(c[0], w0, c[1], pack)
+                a = _stem_conv(s2d, wf, shift, w0.shape[0])
         a = a.permute(0, 3, 1, 2)
         a = conv_norm_forward(c[3], c[3].weight, c[4], 1, 1, a, relu=True)
         a = conv_norm_forward(c[6], c[6].weight, self.bn1, 1, 1, a, relu=True)
