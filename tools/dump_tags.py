@@ -25,4 +25,8 @@ for which in ("fwd", "bwd"):
             info = f"count{arr[k].l[0]} C{arr[k].i[3]} res0"
         elif op == "BN_BWD_APPLY":
             info = f"count{arr[k].l[0]} C{arr[k].i[2]} res{int(arr[k].i[3] > 0)}"
+        elif op == "BN_BWD_FUSED":
+            info = f"count{arr[k].l[0]} npix{arr[k].l[1]} C{arr[k].i[5]} res{int(arr[k].i[3] > 0)}"
+        elif op == "BN_GROUP":
+            info = f"kind{arr[k].i[0]} jobs{arr[k].i[1]}"
         print(which, k, op, tags[k], info)

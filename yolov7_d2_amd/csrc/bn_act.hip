@@ -22,6 +22,23 @@
 #include <stdio.h>
 #include <string.h>
 #include "common.h"
+#ifdef MI_BN_CHAIN_TIMELINE
+// diagnostic build (tools/build_variant.sh bntl "-DMI_BN_CHAIN_TIMELINE" bn_act; tools/bn_chain_timeline.py): thread 0 of every
+// block of a SINGLE-layer fused backward launch stamps the points of the chain between its two phases (wall_clock64, 100 MHz):
+// [0] start  [1] phase-1 loads consumed  [2] block sums in LDS  [3] own atomics acknowledged  [4] arrival counted
+// [5] slots loaded (last block)  [6] totals stored (last)  [7] released (last)  [8] release observed (others)
+// [9] totals in LDS  [10] first dy store issued  [11] end.  mi_debug_bn_timeline copies the stamps out and zeroes them.
+#define BN_TL_POINTS 12
+#define BN_TL_BLOCKS 1024
+__device__ long long g_bn_tl[BN_TL_BLOCKS * BN_TL_POINTS];
+#define BN_TL(k) do { if (threadIdx.x == 0 && blockIdx.x < BN_TL_BLOCKS) g_bn_tl[blockIdx.x * BN_TL_POINTS + (k)] = wall_clock64(); } while (0)
+extern "C" int mi_debug_bn_timeline(long long* host) {
+  void* sym = nullptr;
+  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_bn_tl), sizeof(g_bn_tl)) != hipSuccess) return -1;
+  if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_bn_tl)) != hipSuccess || hipMemset(sym, 0, sizeof(g_bn_tl)) != hipSuccess) return -1;
+  return 0;
+}
+#endif
 #include "bn_common.h"
 #include "conv_bn.h"
 
@@ -499,7 +516,7 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   const bool active = tid < TPB;
   const int c8 = tid % C8, pl = active ? tid / C8 : 0;
   unsigned gen0 = 0;   // thread 0 only
-  if (tid == 0) gen0 = __hip_atomic_load(bn_bar_gen(p.bar, bn_bar_group(bid, nb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) gen0 = bn_bar_generation(p.bar, bid, nb);
   // item = (pixel, channel group); TPB % C8 == 0: the thread's pixels are pix0 + k * pstep.  Addresses are a uniform
   // 64-bit base (+ k * uniform step) plus ONE 32-bit per-thread byte offset per tensor (host checks the 4 GB bound), so
   // the retained items cost no address registers.
@@ -528,8 +545,12 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
       *rp = d;
     }
   };
+  BN_TL(0);
   float dzr[R][8];   // live across the barrier
   float s[2][8];     // (sum dz, sum dz * xhat)
+  // phase 2's per-channel constants do not depend on the sums: they stay in registers across the barrier (loading them again
+  // behind it was one more dependent round trip, 0.5 us of every launch: profiles/bn_bwd_chain_ab.txt)
+  float mu[8], is[8], gi[8];
   {
     bf16x8 dv[R], yv[R];
 #pragma unroll
@@ -539,13 +560,14 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
         yv[u] = *(const bf16x8*)(yb + u * sy + oy);
       }
     }
-    float sc[8], sh[8], mu[8], is[8];
+    float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       sc[e] = p.scale[c8 * 8 + e];
       sh[e] = p.shift[c8 * 8 + e];
       mu[e] = p.mean[c8 * 8 + e];
       is[e] = p.invstd[c8 * 8 + e];
+      gi[e] = p.gamma[c8 * 8 + e] * is[e];
       s[0][e] = s[1][e] = 0.f;
     }
 #pragma unroll
@@ -589,6 +611,9 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
       }
     }
   }
+  BN_TL(1);
+  // (the blocks of a slot reach this together and all sweep the slot's 2 C words from channel 0 up; starting block i of a slot
+  // i waves further on did not shorten the wait for the acknowledgements, it added 0.1 us: profiles/bn_bwd_chain_ab.txt)
   bn_block_sums<2>(red, s, C8, PL, active, pl, c8, p.dacc + (size_t)(bid % p.nslots) * CA * 2, nullptr);
   __shared__ int s_gave_up, s_last;
   // The grid barrier in two halves (conv_bn.h): the block that arrives last folds the nslots accumulator slots of every
@@ -598,26 +623,28 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   // for a 256-channel layer on 512 blocks - measured on the same pattern in round 5's first conv prologue: ~9 us for
   // C = 512 (profiles/r05_bn_bwd_last_arriver_ab.txt; that form is gone).
   bn_bar_arrive(p.bar, bid, nb, &s_gave_up, &s_last);   // (its leading __syncthreads also ends the reads of red[])
+  // the (sum, sum) pair of a channel is one 16-byte word of dacc: the fold and the hand-back move it with ONE agent-scope
+  // (sc1) request per channel - a buffer load / store, which has a 16-byte form with that scope, of the live slots
+  // [0, nslots * CA * 16 bytes); an offset beyond them would read 0 and store nothing (0x00020000: the descriptor's last
+  // word for a raw, unstrided gfx9 buffer - 32-bit data format)
+  const __amdgpu_buffer_rsrc_t accr = __builtin_amdgcn_make_buffer_rsrc((void*)p.dacc, 0, p.nslots * CA * 16, 0x00020000);
+  constexpr int SC1 = 16;   // the instruction's scope bit
   if (s_last) {
     for (int c = tid; c < C; c += 256) {
-      double v1[MI_BN_SLOTS], v2[MI_BN_SLOTS];
+      f64x2 v[MI_BN_SLOTS];
 #pragma unroll
       for (int k = 0; k < MI_BN_SLOTS; ++k) {
-        if (k < p.nslots) {
-          v1[k] = __hip_atomic_load(p.dacc + ((size_t)k * CA + c) * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          v2[k] = __hip_atomic_load(p.dacc + ((size_t)k * CA + c) * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          v1[k] = v2[k] = 0.0;
-        }
+        if (k < p.nslots) v[k] = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(accr, (k * CA + c) * 16, 0, SC1));
+        else v[k] = f64x2{0.0, 0.0};
       }
       double t1 = 0.0, t2 = 0.0;
 #pragma unroll
       for (int k = 0; k < MI_BN_SLOTS; ++k) {
-        t1 += v1[k];
-        t2 += v2[k];
+        t1 += v[k][0];
+        t2 += v[k][1];
       }
-      __hip_atomic_store(p.dacc + (size_t)c * 2, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(p.dacc + (size_t)c * 2 + 1, t2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (c == 0) BN_TL(5);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f64x2{t1, t2}), accr, c * 16, 0, SC1);
       if (p.dbeta) p.dbeta[c] = (float)t1;
       if (p.dgamma) p.dgamma[c] = (float)t2;
     }
@@ -628,22 +655,17 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
   const float poison = s_gave_up ? __builtin_nanf("") : 0.f;
   // ---- phase 2: the finished totals (agent-scope loads: written by a block of another XCD)
   for (int c = tid; c < C; c += 256) {
-    const double t1 = __hip_atomic_load(p.dacc + (size_t)c * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double t2 = __hip_atomic_load(p.dacc + (size_t)c * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_c1[c] = (float)(t1 * p.inv_count) + poison;
-    s_c2[c] = (float)(t2 * p.inv_count) + poison;
+    const f64x2 t = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(accr, c * 16, 0, SC1));
+    s_c1[c] = (float)(t[0] * p.inv_count) + poison;
+    s_c2[c] = (float)(t[1] * p.inv_count) + poison;
   }
   __syncthreads();
+  BN_TL(9);
   if (!active) return;
-  float sc[8], sh[8], mu[8], is[8], gi[8], k1[8], k2[8];
+  float k1[8], k2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = c8 * 8 + e;
-    sc[e] = p.scale[c];
-    sh[e] = p.shift[c];
-    mu[e] = p.mean[c];
-    is[e] = p.invstd[c];
-    gi[e] = p.gamma[c] * is[e];
     k1[e] = s_c1[c];
     k2[e] = s_c2[c];
   }
@@ -661,9 +683,20 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
         o[e] = gi[e] * (dzr[u][e] - k1[e] - xh * k2[e]);
       }
       *(bf16x8*)(dyb + u * sdy + ody) = pack8(o);
+      if (u == 0) BN_TL(10);
     }
   }
   // the streamed items beyond R: recomputed from (da, y), as bn_bwd_apply does
+  if (nmine <= R) {
+    BN_TL(11);
+    return;
+  }
+  float sc[8], sh[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = p.scale[c8 * 8 + e];
+    sh[e] = p.shift[c8 * 8 + e];
+  }
   auto full = [&](const int k, const bf16x8& d, const bf16x8& yy8) {
     float o[8];
 #pragma unroll
@@ -689,6 +722,7 @@ __device__ __forceinline__ void bn_bwd_fused_body(PK& p, const int bid, const in
     for (int u = 0; u < 2; ++u)
       if (k0 + u < nmine) full(k0 + u, d2[u], y2[u]);
   }
+  BN_TL(11);
 }
 
 template <int ACT>

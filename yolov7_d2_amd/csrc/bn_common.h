@@ -7,6 +7,9 @@
 #include "common.h"
 
 #define BN_MAXC 2048
+#ifndef BN_TL   // diagnostic build of bn_act.hip (MI_BN_CHAIN_TIMELINE) only
+#define BN_TL(k) do { } while (0)
+#endif
 // accumulator layout: [slot][CA][2] with CA = C rounded up to 32 - the CoutPad the conv epilogue adds its tile sums with
 #define BN_ACC_C(C) (((C) + 31) / 32 * 32)
 // every tensor access is a 16-byte vector: NULL (an absent optional tensor) passes
@@ -120,6 +123,7 @@ __device__ __forceinline__ void bn_block_sums(float* red, const float (*s)[8], c
       for (int e = 0; e < 8; ++e) red[(pl * C8 + c8) * (8 * NS) + q * 8 + e] = s[q][e];
   }
   __syncthreads();
+  BN_TL(2);
   const int nout = C8 * 8 * NS;
   for (int j = tid; j < nout; j += 256) {
     float acc = 0.f;

@@ -8,77 +8,74 @@
 #pragma once
 #include "common.h"
 #include "bn_common.h"
+#include "bn_barrier.h"
 
 #define BN_FUS_SPIN_LIMIT (1 << 22)
+// diagnostic build of bn_act.hip (MI_BN_CHAIN_TIMELINE): thread 0 of every block stamps point k of the chain; nothing otherwise
+#ifndef BN_TL
+#define BN_TL(k) do { } while (0)
+#endif
 // Grid-wide barrier over nb resident blocks.  Agent-scope atomics are performed memory-side, one after the other per
 // address (~0.1 us each: 512 arrivals on ONE counter cost ~50 us, measured), so arrivals go through a two-level tree -
 // MI_BN_BAR_GROUPS group counters (block % groups), whose last arrivers meet on the top counter - and every group waits
 // on its own generation word; each word sits on its own 256-byte line.  Word layout (uint32):
 //   [0] top arrivals  [2] give-up flag  [64 * (1 + g)] generation of group g  [64 * (1 + G + g)] arrivals of group g
-#define BN_BAR_G MI_BN_BAR_GROUPS
-__device__ __forceinline__ unsigned* bn_bar_gen(unsigned* bar, int g) { return bar + 64 * (1 + g); }
-__device__ __forceinline__ unsigned* bn_bar_cnt(unsigned* bar, int g) { return bar + 64 * (1 + BN_BAR_G + g); }
+// (On the tree a block's arrival, its block barrier included, takes 0.5 us and a release is seen 0.1 us after it is issued:
+// profiles/bn_bwd_chain_ab.txt.)  The protocol itself is bn_barrier.h's, written over an atomics policy so that tests/native/bn_barrier_host.cpp runs the
+// same text on the CPU; BnbHip is the kernel's policy: relaxed agent-scope atomics.
+static_assert(BNB_G == MI_BN_BAR_GROUPS && BNB_WORDS == MI_BN_BAR_WORDS, "bn_barrier.h states the layout of include/mi355_det.h");
+struct BnbHip {
+  static __device__ __forceinline__ unsigned fetch_add(unsigned* p, unsigned v) {
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  static __device__ __forceinline__ void add(unsigned* p, unsigned v) {
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // result unused: no return, no wait
+  }
+  static __device__ __forceinline__ unsigned load(const unsigned* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  static __device__ __forceinline__ void store(unsigned* p, unsigned v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  static __device__ __forceinline__ void pause() { __builtin_amdgcn_s_sleep(8); }
+};
 // No cache maintenance: an agent-scope acquire / release (or __threadfence) writes back and invalidates the XCD's whole L2
 // - issued by hundreds of polling blocks that stalls every block still streaming (measured: +90 us per launch).  It is not
 // needed here: the only data that crosses blocks are the fp64 sums, added by memory-side atomics that have been
 // acknowledged when the block passes its __syncthreads (workgroup release = s_waitcnt vmcnt(0)), and read back after the
-// barrier by agent-scope atomic loads, which bypass the non-coherent caches.
+// barrier by agent-scope (sc1) loads, which bypass the non-coherent caches.
 // *gave_up (LDS) = 1 when this block's wait timed out: its sums are incomplete and it must poison what it writes.
-// thread 0 of a block: the three steps the two barrier halves below are composed of
-__device__ __forceinline__ int bn_bar_group(const int bid, const int nb) { return bid % (nb < BN_BAR_G ? nb : BN_BAR_G); }
-// count this block's arrival; true for the block that arrives last of all (it has reset the counters for the next launch)
-__device__ __forceinline__ bool bn_bar_count(unsigned* bar, const int bid, const int nb) {
-  const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
-  const int g = bid % G;
-  const unsigned gsize = (unsigned)((nb - g + G - 1) / G);
-  if (__hip_atomic_fetch_add(bn_bar_cnt(bar, g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
-    __hip_atomic_store(bn_bar_cnt(bar, g), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)G - 1u) {
-      __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return true;
-    }
-  }
-  return false;
-}
-// the last block: let every group go
-__device__ __forceinline__ void bn_bar_release(unsigned* bar, const int nb) {
-  const int G = nb < BN_BAR_G ? nb : BN_BAR_G;
-  for (int q = 0; q < G; ++q) __hip_atomic_fetch_add(bn_bar_gen(bar, q), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// wait until the generation of this block's group has moved on from gen0; true when the wait gave up
-__device__ __forceinline__ bool bn_bar_wait(unsigned* bar, const unsigned gen0, const int bid, const int nb) {
-  int spins = 0;
-  while (__hip_atomic_load(bn_bar_gen(bar, bn_bar_group(bid, nb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen0) {
-    __builtin_amdgcn_s_sleep(8);
-    if (++spins > BN_FUS_SPIN_LIMIT) {  // a block that never became resident: report instead of hanging the GPU
-      __hip_atomic_store(bar + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return true;
-    }
-  }
-  return false;
-}
-
 // The barrier in two halves, so that the block that arrives LAST can do work for everybody before it releases the
 // others (bn_bwd_fused: it folds the accumulator slots into one total per channel - one block's worth of loads instead of
 // every block's; see bn_act.hip).  *is_last / *gave_up live in LDS.
+__device__ __forceinline__ unsigned bn_bar_generation(unsigned* bar, const int bid, const int nb) {
+  return bnb_generation<BnbHip>(bar, bid, nb);
+}
 __device__ __forceinline__ void bn_bar_arrive(unsigned* bar, const int bid, const int nb, int* gave_up, int* is_last) {
   // every thread's fp64 atomicAdds must have been acknowledged before thread 0 counts the arrival: stated explicitly - the
   // memory model does not promise that a workgroup-scope barrier waits for vmcnt(0)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  BN_TL(3);
   __syncthreads();
   if (threadIdx.x == 0) {
     *gave_up = 0;
-    *is_last = bn_bar_count(bar, bid, nb) ? 1 : 0;
+    *is_last = bnb_arrive<BnbHip>(bar, bid, nb) ? 1 : 0;
+    BN_TL(4);
   }
   __syncthreads();
 }
 __device__ __forceinline__ void bn_bar_finish(unsigned* bar, const unsigned gen0, const int bid, const int nb, int* gave_up,
                                               const int* is_last) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last block's agent-scope stores of the folded totals: acknowledged
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last block's write-through stores of the folded totals: acknowledged
   __syncthreads();
-  if (threadIdx.x == 0) {
-    if (*is_last) bn_bar_release(bar, nb);
-    else if (bn_bar_wait(bar, gen0, bid, nb)) *gave_up = 1;
+  if (*is_last) {
+    // one lane per group: the bumps leave in one instruction and nobody waits for what they return
+    BN_TL(6);
+    if ((int)threadIdx.x < bnb_groups(nb)) bnb_release_group<BnbHip>(bar, (int)threadIdx.x);
+    BN_TL(7);
+  } else if (threadIdx.x == 0) {
+    if (bnb_wait<BnbHip>(bar, gen0, bid, nb, BN_FUS_SPIN_LIMIT)) *gave_up = 1;
+    BN_TL(8);
   }
   __syncthreads();
 }
