@@ -348,6 +348,51 @@ int mi_rcda_fwd(const mi_rcda_desc* d, mi_stream_t s);
 int64_t mi_rcda_bwd_ws_bytes(const mi_rcda_desc* d);
 int mi_rcda_bwd(const mi_rcda_desc* d, mi_stream_t s);
 
+/* ---- SMCA: attention with a Gaussian-like spatial prior (csrc/mha.hip, the PRIOR instantiations) ------------
+ * The cross-attention of SMCA-DETR's decoder (backbone/smcadetr_backbone.py:285-315, layers/smca_attention.py:277-278),
+ * head_dim 32, operands as mi_mha_*_ld (bf16 [L][B][E] sequence-first, mask uint8 [B][Lk], lse fp32 [B][H][Lq]):
+ *   logit[q][key] = scale * Q[q].K[key] + (mask[key] ? -inf : 0) + G[q][key]
+ *   G[q][key]     = -| a dx^2 + b dy^2 + c dx^2 dy^2 | * inv_smooth,   dx = px - key % map_w,  dy = py - key / map_w
+ *   O = dropout(softmax(logit)) V
+ * point: fp32 [Lq][B][H][2] = (px, py); coef: fp32 [Lq][B][H][3] = (a, b, c), both contiguous; Lk == map_h * map_w.
+ * The prior is evaluated in registers: no [B*H, Lq, Lk] tensor exists.  The backward also writes dpoint / dcoef (fp32, the
+ * operands' shapes; d|x|/dx = sign(x), 0 at 0): row sums of the score gradient taken inside the dQ kernel in a fixed order
+ * (no atomics, no workspace: bit-reproducible).  A fully padded query row gives O = 0, lse = -inf and zero gradients.
+ * The dropout element index is mi_mha_dropout_mask's.  o_f32 (may be NULL): fp32 copy of O, written by the forward and read
+ * by the backward's delta.  delta: fp32 [B][H][Lq] scratch of the backward.  Argument errors (null pointers, E != 32 H,
+ * Lk != map_h * map_w, misaligned operands, Lq * Lk >= 2^32, drop_p outside [0, 1), inv_smooth not finite and positive)
+ * return MI_EINVAL before any launch.  No entry allocates, reads back or synchronises. */
+typedef struct mi_smca_desc {
+  const void* q;
+  const void* k;
+  const void* v;
+  const uint8_t* mask;  /* may be NULL                                                */
+  const float* point;
+  const float* coef;
+  void* o;
+  float* o_f32;         /* may be NULL                                                */
+  float* lse;
+  const void* dout;     /* backward only from here                                    */
+  float* delta;
+  void* dq;
+  void* dk;
+  void* dv;
+  float* dpoint;
+  float* dcoef;
+  uint64_t seed;
+  int32_t B, H, Lq, Lk, E;
+  int32_t ldq, ldk;     /* row strides of q / dq and k / dk (>= E, multiples of 8)    */
+  int32_t map_h, map_w;
+  int32_t rsv_;
+  float scale;          /* head_dim^-0.5 in the module                                */
+  float inv_smooth;     /* 1 / smooth                                                 */
+  float drop_p;
+  float rsv2_;
+} mi_smca_desc;
+int mi_smca_desc_size(void);   /* sizeof(mi_smca_desc) as compiled (binding self-check) */
+int mi_smca_fwd(const mi_smca_desc* d, mi_stream_t s);
+int mi_smca_bwd(const mi_smca_desc* d, mi_stream_t s);
+
 /* ---- depthwise 3x3 convolution ------------------------------------------------
  * the `dconv` of DWConv (backbone/layers/wrappers.py:86-102: BaseConv(C, C, ksize, stride, groups=C); the reference
  * builds it with ksize 3 everywhere, darknetx.py:113-160): NHWC bf16, pad 1, stride 1 or 2, C % 8 == 0.

@@ -124,6 +124,14 @@ class mi_rcda_desc(C.Structure):
                [("scale", C.c_float), ("rsv_", C.c_int32)]
 
 
+class mi_smca_desc(C.Structure):
+    """attention with SMCA's Gaussian prior (csrc/mha.hip, PRIOR instantiations): one record for the forward and the backward"""
+    _fields_ = [(n, C.c_void_p) for n in ("q", "k", "v", "mask", "point", "coef", "o", "o_f32", "lse", "dout", "delta", "dq", "dk", "dv",
+                                          "dpoint", "dcoef")] + [("seed", C.c_uint64)] + \
+               [(n, C.c_int32) for n in ("B", "H", "Lq", "Lk", "E", "ldq", "ldk", "map_h", "map_w", "rsv_")] + \
+               [(n, C.c_float) for n in ("scale", "inv_smooth", "drop_p", "rsv2_")]
+
+
 class mi_bn_relu_norm(C.Structure):
     """one norm operand of mi_bn_relu_desc (csrc/bn_relu.hip)"""
     _fields_ = [(n, C.c_void_p) for n in ("y", "acc", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked",
@@ -312,6 +320,9 @@ _PROTOS = {
     "mi_rcda_fwd": (C.c_int, [C.POINTER(mi_rcda_desc), _vp]),
     "mi_rcda_bwd_ws_bytes": (C.c_int64, [C.POINTER(mi_rcda_desc)]),
     "mi_rcda_bwd": (C.c_int, [C.POINTER(mi_rcda_desc), _vp]),
+    "mi_smca_desc_size": (C.c_int, []),
+    "mi_smca_fwd": (C.c_int, [C.POINTER(mi_smca_desc), _vp]),
+    "mi_smca_bwd": (C.c_int, [C.POINTER(mi_smca_desc), _vp]),
     "mi_bn_relu_desc_size": (C.c_int, []),
     "mi_bn_stats": (C.c_int, [_vp, _i, _i64, _i, _vp, _i, _vp]),
     "mi_bn_relu_fwd": (C.c_int, [C.POINTER(mi_bn_relu_desc), _vp]),

@@ -55,6 +55,28 @@ struct MhaK {
   const unsigned long long* seed_off;   // device word added to seed (mi_dropout_seed_offset) or NULL
 };
 
+// SMCA's Gaussian prior (smcadetr_backbone.py:285-310, smca_attention.py:277-278) as a closed form added to the logit:
+//   G[q][key] = -| a dx^2 + b dy^2 + c dx^2 dy^2 | * inv_smooth,  dx = px - key % map_w,  dy = py - key / map_w
+// with (px, py) = point[q][b][h][0..1] and (a, b, c) = coef[q][b][h][0..2].  The PRIOR instantiations of the three kernels
+// take this record; the plain ones keep MhaK, so their argument block and code are what they were.
+struct SmcaK : MhaK {
+  const float* point;   // [Lq][B][H][2]
+  const float* coef;    // [Lq][B][H][3]
+  float* dpoint;        // backward
+  float* dcoef;
+  int map_w;
+  float inv_smooth;
+  float gs;             // inv_smooth / scale: the prior in raw score units (it enters the score MFMA's accumulator)
+};
+template <bool PRIOR> struct MhaArgs { typedef MhaK type; };
+template <> struct MhaArgs<true> { typedef SmcaK type; };
+
+// one query's (or, in the dK / dV kernel, four queries') prior against one key, in raw score units: x * gs with the
+// coefficients pre-multiplied by gs; t = a + c dy^2 is also the factor of dG / dpx
+__device__ __forceinline__ float smca_x(float dx2, float dy2, float a, float b, float c) {
+  return __builtin_fmaf(dx2, __builtin_fmaf(c, dy2, a), b * dy2);
+}
+
 // rk: mha_rng_key(p), taken ONCE at the top of a kernel (the seed word is a uniform load + a 64-bit hash: not per element).
 // The element index is the linear index into [B][H][Lq][Lk] (what mi_mha_dropout_mask enumerates): a uniform 64-bit base
 // per (b, h) plus a 32-bit offset q * Lk + key (the launchers require Lq * Lk < 2^32)
@@ -124,11 +146,16 @@ struct MhaChunk {
   }
 };
 
-template <bool DROP>
-__global__ __launch_bounds__(768) void mha_fwd2_kernel(const MhaK p) {
+template <bool DROP, bool PRIOR = false>
+__global__ __launch_bounds__(768) void mha_fwd2_kernel(const typename MhaArgs<PRIOR>::type p) {
   const unsigned long long rk = mha_rng_key(p);
   __shared__ __attribute__((aligned(16))) char Ks[2 * 8192], Vs[2 * 8192];
   __shared__ __attribute__((aligned(16))) float Mb[2][MHA2_KC];
+  float* kxy = nullptr;   // PRIOR: the chunk's key coordinates beside Mb, [buf][x | y][MHA2_KC]
+  if constexpr (PRIOR) {
+    __shared__ __attribute__((aligned(16))) float Kxy[2][2][MHA2_KC];
+    kxy = &Kxy[0][0][0];
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nth = blockDim.x;
   const int t = lane & 15, g = lane >> 4;
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
@@ -136,6 +163,17 @@ __global__ __launch_bounds__(768) void mha_fwd2_kernel(const MhaK p) {
   const int myq = q0 + t;
   bf16x8 qf = {};
   if (myq < p.Lq) qf = *(const bf16x8*)(p.q + ((size_t)myq * p.B + b) * p.ldq + h * MHA_D + g * 8);
+  float px = 0.f, py = 0.f, ca = 0.f, cb = 0.f, cc = 0.f;   // PRIOR: query t's point and its coefficients times gs
+  if constexpr (PRIOR) {
+    if (myq < p.Lq) {
+      const size_t qi = ((size_t)myq * p.B + b) * p.H + h;
+      px = p.point[qi * 2];
+      py = p.point[qi * 2 + 1];
+      ca = p.coef[qi * 3] * p.gs;
+      cb = p.coef[qi * 3 + 1] * p.gs;
+      cc = p.coef[qi * 3 + 2] * p.gs;
+    }
+  }
   f32x4 oacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   f32x4 lacc = {0.f, 0.f, 0.f, 0.f};                       // normaliser, same layout as oacc (every column alike)
   float m_run = -INFINITY, neg_m = 0.f, l_part = 0.f;      // reference maximum of query t in raw score units; -m * sc2
@@ -160,6 +198,11 @@ __global__ __launch_bounds__(768) void mha_fwd2_kernel(const MhaK p) {
     kv.store(Ks, Vs, buf, tid, nth);
     const int key = c * MHA2_KC + (tid & (MHA2_KC - 1));
     Mb[buf][tid & (MHA2_KC - 1)] = (key >= p.Lk || (p.mask && mreg)) ? -INFINITY : 0.f;
+    if constexpr (PRIOR) {
+      const int ky = key / p.map_w;
+      kxy[buf * 2 * MHA2_KC + (tid & (MHA2_KC - 1))] = (float)(key - ky * p.map_w);
+      kxy[buf * 2 * MHA2_KC + MHA2_KC + (tid & (MHA2_KC - 1))] = (float)ky;
+    }
   };
   load_chunk(0);
   store_chunk(0);
@@ -174,7 +217,16 @@ __global__ __launch_bounds__(768) void mha_fwd2_kernel(const MhaK p) {
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
       const bf16x8 kf = frag_rows(Ks + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
-      const f32x4 bias = *(const f32x4*)(&Mb[cur][16 * a + 4 * g]);
+      f32x4 bias = *(const f32x4*)(&Mb[cur][16 * a + 4 * g]);
+      if constexpr (PRIOR) {
+        const f32x4 kx = *(const f32x4*)(kxy + cur * 2 * MHA2_KC + 16 * a + 4 * g);
+        const f32x4 ky = *(const f32x4*)(kxy + cur * 2 * MHA2_KC + MHA2_KC + 16 * a + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float dx = px - kx[r], dy = py - ky[r];
+          bias[r] -= fabsf(smca_x(dx * dx, dy * dy, ca, cb, cc));
+        }
+      }
       s[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, bias, 0, 0, 0);
     }
     float mx = fmaxf(s[0][0], s[0][1]);
@@ -291,11 +343,16 @@ __global__ __launch_bounds__(256) void mha_delta_kernel(const MhaK p, float* del
 // product's (dQ) or is applied to the finished rows (dK / dV: a padded key's rows are computed and discarded); the
 // softmax scale multiplies the accumulators once at the end.
 // dQ: a wave owns 16 queries (as the forward), streams K / V
-template <bool DROP>
-__global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const MhaK p) {
+template <bool DROP, bool PRIOR = false>
+__global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const typename MhaArgs<PRIOR>::type p) {
   const unsigned long long rk = mha_rng_key(p);
   __shared__ __attribute__((aligned(16))) char Ks[2 * 8192], Vs[2 * 8192];
   __shared__ __attribute__((aligned(16))) float Mb[2][MHA2_KC];
+  float* kxy = nullptr;
+  if constexpr (PRIOR) {
+    __shared__ __attribute__((aligned(16))) float Kxy[2][2][MHA2_KC];
+    kxy = &Kxy[0][0][0];
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nth = blockDim.x;
   const int t = lane & 15, g = lane >> 4;
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
@@ -310,6 +367,19 @@ __global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const MhaK p) {
     const float lse = p.lse[((size_t)b * p.H + h) * p.Lq + myq];
     neg_l = lse == -INFINITY ? -INFINITY : -lse * 1.44269504088896341f;
     dl = p.delta[((size_t)b * p.H + h) * p.Lq + myq];
+  }
+  // PRIOR: query t's point, its coefficients times gs, and its five gradient sums over this lane's keys (fp32, of ds before
+  // its bf16 pack): ga, gb, gc = sum ds sign(x) {dx^2, dy^2, dx^2 dy^2}; gx, gy = sum ds sign(x) {dx (a + c dy^2), dy (b + c dx^2)}
+  float px = 0.f, py = 0.f, ca = 0.f, cb = 0.f, cc = 0.f, ga = 0.f, gb = 0.f, gc = 0.f, gx = 0.f, gy = 0.f;
+  if constexpr (PRIOR) {
+    if (myq < p.Lq) {
+      const size_t qi = ((size_t)myq * p.B + b) * p.H + h;
+      px = p.point[qi * 2];
+      py = p.point[qi * 2 + 1];
+      ca = p.coef[qi * 3] * p.gs;
+      cb = p.coef[qi * 3 + 1] * p.gs;
+      cc = p.coef[qi * 3 + 2] * p.gs;
+    }
   }
   const float sc2 = p.scale * 1.44269504088896341f;
   f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -329,6 +399,11 @@ __global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const MhaK p) {
     kv.store(Ks, Vs, buf, tid, nth);
     const int key = c * MHA2_KC + (tid & (MHA2_KC - 1));
     Mb[buf][tid & (MHA2_KC - 1)] = (key >= p.Lk || (p.mask && mreg)) ? -INFINITY : 0.f;
+    if constexpr (PRIOR) {
+      const int ky = key / p.map_w;
+      kxy[buf * 2 * MHA2_KC + (tid & (MHA2_KC - 1))] = (float)(key - ky * p.map_w);
+      kxy[buf * 2 * MHA2_KC + MHA2_KC + (tid & (MHA2_KC - 1))] = (float)ky;
+    }
   };
   load_chunk(0);
   store_chunk(0);
@@ -337,32 +412,60 @@ __global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const MhaK p) {
     const int cur = c & 1;
     if (c + 1 < nchunks) load_chunk(c + 1);
     const int k0 = c * MHA2_KC;
-    // S^T and dP^T - delta: lane (t = query, g): [a][r] = key k0 + 16 a + 4 g + r
-    f32x4 s[8], dp[8];
+    // S^T and dP^T - delta: lane (t = query, g): [a][r] = key k0 + 16 a + 4 g + r.  All eight tile pairs of the chunk up
+    // front (PRIOR: one 32-key tile at a time - the prior's terms of a tile stay in registers from the bias to the sums)
+    constexpr int TG = PRIOR ? 1 : 4;
+#pragma unroll 1
+    for (int tg = 0; tg < 4; tg += TG) {   // (a real loop with the prior: unrolled, the scheduler hoists all four tiles' terms)
+      f32x4 s[2 * TG], dp[2 * TG];
 #pragma unroll
-    for (int a = 0; a < 8; ++a) {
-      const bf16x8 kf = frag_rows(Ks + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
-      const bf16x8 vf = frag_rows(Vs + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
-      const f32x4 bias = *(const f32x4*)(&Mb[cur][16 * a + 4 * g]);
-      s[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, bias, 0, 0, 0);
-      dp[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof, ndl, 0, 0, 0);
-    }
+      for (int aa = 0; aa < 2 * TG; ++aa) {
+        const int a = 2 * tg + aa;
+        const bf16x8 kf = frag_rows(Ks + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
+        const bf16x8 vf = frag_rows(Vs + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
+        f32x4 bias = *(const f32x4*)(&Mb[cur][16 * a + 4 * g]);
+        if constexpr (PRIOR) {
+          const f32x4 kx = *(const f32x4*)(kxy + cur * 2 * MHA2_KC + 16 * a + 4 * g);
+          const f32x4 ky = *(const f32x4*)(kxy + cur * 2 * MHA2_KC + MHA2_KC + 16 * a + 4 * g);
 #pragma unroll
-    for (int t2 = 0; t2 < 4; ++t2) {
-      bf16x8 dsf;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int a = 2 * t2 + (e >> 2), r = e & 3;
-        const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[a][r], sc2, neg_l));   // (masked key: s = -inf -> 0)
-        float ds;
-        if constexpr (DROP) ds = pe * (dp[a][r] * mha_keep(p, rk, b, h, myq, k0 + 16 * a + 4 * g + r) - dl);
-        else ds = pe * dp[a][r];
-        dsf[e] = (__bf16)ds;
+          for (int r = 0; r < 4; ++r) {
+            const float dx = px - kx[r], dy = py - ky[r];
+            bias[r] -= fabsf(smca_x(dx * dx, dy * dy, ca, cb, cc));
+          }
+        }
+        s[aa] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, bias, 0, 0, 0);
+        dp[aa] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof, ndl, 0, 0, 0);
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bf16x8 kc = frag_cols(Ks + cur * 8192 + t2 * 2048, j, t, g);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf, kc, acc[j], 0, 0, 0);
+      for (int tt = 0; tt < TG; ++tt) {
+        const int t2 = tg + tt;
+        bf16x8 dsf;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int a = 2 * t2 + (e >> 2), aa = 2 * tt + (e >> 2), r = e & 3;
+          const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[aa][r], sc2, neg_l));   // (masked key: s = -inf -> 0)
+          float ds;
+          if constexpr (DROP) ds = pe * (dp[aa][r] * mha_keep(p, rk, b, h, myq, k0 + 16 * a + 4 * g + r) - dl);
+          else ds = pe * dp[aa][r];
+          dsf[e] = (__bf16)ds;
+          if constexpr (PRIOR) {
+            const int kk = 16 * a + 4 * g + r;
+            const float dx = px - kxy[cur * 2 * MHA2_KC + kk], dy = py - kxy[cur * 2 * MHA2_KC + MHA2_KC + kk];
+            const float dx2 = dx * dx, dy2 = dy * dy;
+            const float x = smca_x(dx2, dy2, ca, cb, cc);
+            const float w = x > 0.f ? ds : (x < 0.f ? -ds : 0.f);   // ds * sign(x), sign(0) = 0
+            ga = __builtin_fmaf(w, dx2, ga);
+            gb = __builtin_fmaf(w, dy2, gb);
+            gc = __builtin_fmaf(w * dx2, dy2, gc);
+            gx = __builtin_fmaf(w * dx, __builtin_fmaf(cc, dy2, ca), gx);
+            gy = __builtin_fmaf(w * dy, __builtin_fmaf(cc, dx2, cb), gy);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const bf16x8 kc = frag_cols(Ks + cur * 8192 + t2 * 2048, j, t, g);
+          acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf, kc, acc[j], 0, 0, 0);
+        }
       }
     }
     if (c + 1 < nchunks) store_chunk(c + 1);
@@ -376,14 +479,37 @@ __global__ __launch_bounds__(768) void mha_bwd_dq2_kernel(const MhaK p) {
       op[16 + t] = (__bf16)(acc[1][r] * p.scale);
     }
   }
+  if constexpr (PRIOR) {
+    // dG / d(a, b, c) = -sign(x) inv_smooth {dx^2, dy^2, dx^2 dy^2};  dG / dpx = -sign(x) inv_smooth 2 dx (a + c dy^2) - and
+    // the kernel's a, c carry gs = inv_smooth / scale already.  The four lanes of a query close the sums; lane g = 0 stores.
+    float* const sums[5] = {&ga, &gb, &gc, &gx, &gy};
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      *sums[i] += __shfl_xor(*sums[i], 16, 64);
+      *sums[i] += __shfl_xor(*sums[i], 32, 64);
+    }
+    if (g == 0 && myq < p.Lq) {
+      const size_t qi = ((size_t)myq * p.B + b) * p.H + h;
+      p.dcoef[qi * 3] = -p.inv_smooth * ga;
+      p.dcoef[qi * 3 + 1] = -p.inv_smooth * gb;
+      p.dcoef[qi * 3 + 2] = -p.inv_smooth * gc;
+      p.dpoint[qi * 2] = -2.f * p.scale * gx;
+      p.dpoint[qi * 2 + 1] = -2.f * p.scale * gy;
+    }
+  }
 }
 
 // dK, dV: a wave owns 16 keys, streams Q / dO with the queries' -lse * log2(e) and -delta
-template <bool DROP>
-__global__ __launch_bounds__(768) void mha_bwd_dkv2_kernel(const MhaK p) {
+template <bool DROP, bool PRIOR = false>
+__global__ __launch_bounds__(768) void mha_bwd_dkv2_kernel(const typename MhaArgs<PRIOR>::type p) {
   const unsigned long long rk = mha_rng_key(p);
   __shared__ __attribute__((aligned(16))) char Qs[2 * 8192], Ds[2 * 8192];
   __shared__ __attribute__((aligned(16))) float Nl[2][MHA2_KC], Nd[2][MHA2_KC];
+  float* qpr = nullptr;   // PRIOR: the chunk's queries' px, py, a gs, b gs, c gs beside Nl / Nd, [buf][5][MHA2_KC]
+  if constexpr (PRIOR) {
+    __shared__ __attribute__((aligned(16))) float Qpr[2][5][MHA2_KC];
+    qpr = &Qpr[0][0][0];
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nth = blockDim.x;
   const int t = lane & 15, g = lane >> 4;
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
@@ -404,12 +530,27 @@ __global__ __launch_bounds__(768) void mha_bwd_dkv2_kernel(const MhaK p) {
   float lreg = 0.f, ereg = 0.f;
   const float* const lrow = p.lse + ((size_t)b * p.H + h) * p.Lq;
   const float* const drow = p.delta + ((size_t)b * p.H + h) * p.Lq;
+  float kx = 0.f, ky = 0.f, preg[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // PRIOR: key t's grid cell; this thread's staged query
+  if constexpr (PRIOR) {
+    const int kk = mykey < p.Lk ? mykey : p.Lk - 1;
+    const int kyi = kk / p.map_w;
+    kx = (float)(kk - kyi * p.map_w);
+    ky = (float)kyi;
+  }
   auto load_chunk = [&](int c) {
     const int r0 = c * MHA2_KC;
     qd.load(p.q, p.ldq, p.dout, p.E, r0, p.Lq, p.B, b, h, tid, nth);
     const int qq = r0 + (tid & (MHA2_KC - 1));
     lreg = lrow[qq < p.Lq ? qq : p.Lq - 1];
     ereg = drow[qq < p.Lq ? qq : p.Lq - 1];
+    if constexpr (PRIOR) {
+      const size_t qi = ((size_t)(qq < p.Lq ? qq : p.Lq - 1) * p.B + b) * p.H + h;
+      preg[0] = p.point[qi * 2];
+      preg[1] = p.point[qi * 2 + 1];
+      preg[2] = p.coef[qi * 3];
+      preg[3] = p.coef[qi * 3 + 1];
+      preg[4] = p.coef[qi * 3 + 2];
+    }
   };
   auto store_chunk = [&](int c) {
     const int buf = c & 1;
@@ -418,6 +559,10 @@ __global__ __launch_bounds__(768) void mha_bwd_dkv2_kernel(const MhaK p) {
     const bool live = qq < p.Lq && lreg != -INFINITY;   // (a fully masked query row contributes nothing)
     Nl[buf][tid & (MHA2_KC - 1)] = live ? -lreg * 1.44269504088896341f : -INFINITY;
     Nd[buf][tid & (MHA2_KC - 1)] = qq < p.Lq ? -ereg : 0.f;
+    if constexpr (PRIOR) {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) qpr[(buf * 5 + i) * MHA2_KC + (tid & (MHA2_KC - 1))] = i < 2 ? preg[i] : preg[i] * p.gs;
+    }
   };
   load_chunk(0);
   store_chunk(0);
@@ -438,7 +583,18 @@ __global__ __launch_bounds__(768) void mha_bwd_dkv2_kernel(const MhaK p) {
         const bf16x8 qa = frag_rows(Qs + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
         const bf16x8 da = frag_rows(Ds + cur * 8192 + (a >> 1) * 2048, a & 1, t, g);
         const f32x4 nd = DROP ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(&Nd[cur][16 * a + 4 * g]);
-        s[aa] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        f32x4 gbias = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (PRIOR) {
+          const float* const qp = qpr + cur * 5 * MHA2_KC + 16 * a + 4 * g;
+          const f32x4 qx = *(const f32x4*)qp, qy = *(const f32x4*)(qp + MHA2_KC), qa3 = *(const f32x4*)(qp + 2 * MHA2_KC);
+          const f32x4 qb3 = *(const f32x4*)(qp + 3 * MHA2_KC), qc3 = *(const f32x4*)(qp + 4 * MHA2_KC);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float dx = qx[r] - kx, dy = qy[r] - ky;
+            gbias[r] -= fabsf(smca_x(dx * dx, dy * dy, qa3[r], qb3[r], qc3[r]));
+          }
+        }
+        s[aa] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf, gbias, 0, 0, 0);
         dp[aa] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf, nd, 0, 0, 0);
       }
 #pragma unroll
@@ -634,5 +790,84 @@ extern "C" int mi_mha_bwd_dropout_ld(const void* q, int ldq, const void* k, int 
   if (p.drop_thr) hipLaunchKernelGGL(mha_bwd_dkv2_kernel<true>, gk, dim3(nk * 64), 0, s, p);
   else hipLaunchKernelGGL(mha_bwd_dkv2_kernel<false>, gk, dim3(nk * 64), 0, s, p);
   MI_CHECK_LAUNCH("mha_bwd_dkv2");
+  return MI_OK;
+}
+
+// ------------------------------------------------------------------ SMCA: the same three kernels with the Gaussian prior
+extern "C" int mi_smca_desc_size(void) { return (int)sizeof(mi_smca_desc); }
+
+// finite and > 0, read off the bits (this file is compiled with -fno-honor-nans: a comparison may not see a NaN)
+static bool smca_finite_pos(float x) {
+  uint32_t u;
+  memcpy(&u, &x, 4);
+  return (u >> 31) == 0 && ((u >> 23) & 0xffu) != 0xffu && u != 0u;
+}
+
+static int smca_fill(const mi_smca_desc* d, SmcaK* p, const char* who) {
+  MI_REQUIRE(d, "%s: null descriptor", who);
+  MI_REQUIRE(d->q && d->k && d->v && d->point && d->coef && d->lse, "%s: null operand", who);
+  MI_REQUIRE(d->B > 0 && d->H > 0 && d->Lq > 0 && d->Lk > 0 && d->E == d->H * MHA_D, "%s: E %d must be H*%d (H %d)", who, d->E, MHA_D, d->H);
+  MI_REQUIRE(d->map_h > 0 && d->map_w > 0 && (long long)d->map_h * d->map_w == d->Lk, "%s: Lk %d must be map_h * map_w (%d x %d)", who,
+             d->Lk, d->map_h, d->map_w);
+  MI_REQUIRE(((uintptr_t)d->q % 16) == 0 && ((uintptr_t)d->k % 16) == 0 && ((uintptr_t)d->v % 16) == 0, "%s: q / k / v not aligned to 16 bytes", who);
+  MI_REQUIRE(((uintptr_t)d->point % 4) == 0 && ((uintptr_t)d->coef % 4) == 0 && ((uintptr_t)d->lse % 4) == 0,
+             "%s: point / coef / lse not aligned to 4 bytes", who);
+  MI_REQUIRE(!d->o_f32 || ((uintptr_t)d->o_f32 % 16) == 0, "%s: o_f32 not aligned to 16 bytes", who);
+  MI_REQUIRE((long long)d->B * d->H < 65536, "%s: B*H too large", who);
+  MI_REQUIRE((long long)d->Lq * d->Lk < (1LL << 32), "%s: Lq * Lk must stay below 2^32 (32-bit score offsets inside a head)", who);
+  MI_REQUIRE(d->ldq >= d->E && d->ldk >= d->E && d->ldq % 8 == 0 && d->ldk % 8 == 0, "%s: row strides ldq %d / ldk %d (>= E, multiples of 8)",
+             who, d->ldq, d->ldk);
+  MI_REQUIRE(smca_finite_pos(d->inv_smooth), "%s: inv_smooth %f must be finite and positive", who, d->inv_smooth);
+  MI_REQUIRE(smca_finite_pos(d->scale), "%s: scale %f must be finite and positive", who, d->scale);
+  // drop_p: +-0, or finite and positive (a NaN or an infinity is refused here; mha_set_dropout then checks the range)
+  uint32_t dbits;
+  memcpy(&dbits, &d->drop_p, 4);
+  MI_REQUIRE((dbits & 0x7fffffffu) == 0u || smca_finite_pos(d->drop_p), "%s: dropout p %f must be in [0, 1)", who, d->drop_p);
+  memset(p, 0, sizeof(*p));
+  const int rc = mha_set_dropout(p, d->drop_p, d->seed);
+  if (rc) return rc;
+  p->q = (const __bf16*)d->q; p->k = (const __bf16*)d->k; p->v = (const __bf16*)d->v; p->mask = d->mask;
+  p->o = (__bf16*)d->o; p->o32 = d->o_f32; p->lse = d->lse; p->B = d->B; p->H = d->H; p->Lq = d->Lq; p->Lk = d->Lk; p->E = d->E;
+  p->ldq = d->ldq; p->ldk = d->ldk; p->scale = d->scale;
+  p->point = d->point; p->coef = d->coef; p->map_w = d->map_w; p->inv_smooth = d->inv_smooth; p->gs = d->inv_smooth / d->scale;
+  return MI_OK;
+}
+
+extern "C" int mi_smca_fwd(const mi_smca_desc* d, mi_stream_t st) {
+  SmcaK p;
+  const int rc = smca_fill(d, &p, "smca_fwd");
+  if (rc) return rc;
+  MI_REQUIRE(d->o, "smca_fwd: null output");
+  MI_REQUIRE(((uintptr_t)d->o % 2) == 0, "smca_fwd: o not aligned");
+  const int nwv = mha2_waves(p.Lq, p.B * p.H);
+  const dim3 grid(mi_cdiv(mi_cdiv(p.Lq, 16), nwv), p.B * p.H), blk(nwv * 64);
+  if (p.drop_thr) hipLaunchKernelGGL((mha_fwd2_kernel<true, true>), grid, blk, 0, (hipStream_t)st, p);
+  else hipLaunchKernelGGL((mha_fwd2_kernel<false, true>), grid, blk, 0, (hipStream_t)st, p);
+  MI_CHECK_LAUNCH("smca_fwd");
+  return MI_OK;
+}
+
+extern "C" int mi_smca_bwd(const mi_smca_desc* d, mi_stream_t st) {
+  SmcaK p;
+  const int rc = smca_fill(d, &p, "smca_bwd");
+  if (rc) return rc;
+  MI_REQUIRE(d->o && d->dout && d->delta && d->dq && d->dk && d->dv && d->dpoint && d->dcoef, "smca_bwd: null");
+  MI_REQUIRE(((uintptr_t)d->dq % 16) == 0 && ((uintptr_t)d->dk % 16) == 0 && ((uintptr_t)d->dout % 16) == 0 && ((uintptr_t)d->o % 16) == 0,
+             "smca_bwd: o / dout / dq / dk not aligned to 16 bytes");
+  MI_REQUIRE(((uintptr_t)d->delta % 4) == 0 && ((uintptr_t)d->dpoint % 4) == 0 && ((uintptr_t)d->dcoef % 4) == 0 && ((uintptr_t)d->dv % 2) == 0,
+             "smca_bwd: delta / dpoint / dcoef / dv not aligned");
+  p.dout = (const __bf16*)d->dout; p.delta = d->delta; p.dq = (__bf16*)d->dq; p.dk = (__bf16*)d->dk; p.dv = (__bf16*)d->dv;
+  p.dpoint = d->dpoint; p.dcoef = d->dcoef;
+  hipStream_t s = (hipStream_t)st;
+  hipLaunchKernelGGL(mha_delta_kernel, dim3(mi_cdiv(p.B * p.H * p.Lq * 4, 256)), dim3(256), 0, s, (MhaK)p, d->delta);
+  MI_CHECK_LAUNCH("smca_delta");
+  const int nq = mha2_waves(p.Lq, p.B * p.H), nk = mha2_waves(p.Lk, p.B * p.H);
+  const dim3 gq(mi_cdiv(mi_cdiv(p.Lq, 16), nq), p.B * p.H), gk(mi_cdiv(mi_cdiv(p.Lk, 16), nk), p.B * p.H);
+  if (p.drop_thr) hipLaunchKernelGGL((mha_bwd_dq2_kernel<true, true>), gq, dim3(nq * 64), 0, s, p);
+  else hipLaunchKernelGGL((mha_bwd_dq2_kernel<false, true>), gq, dim3(nq * 64), 0, s, p);
+  MI_CHECK_LAUNCH("smca_bwd_dq");
+  if (p.drop_thr) hipLaunchKernelGGL((mha_bwd_dkv2_kernel<true, true>), gk, dim3(nk * 64), 0, s, p);
+  else hipLaunchKernelGGL((mha_bwd_dkv2_kernel<false, true>), gk, dim3(nk * 64), 0, s, p);
+  MI_CHECK_LAUNCH("smca_bwd_dkv");
   return MI_OK;
 }

@@ -12,6 +12,8 @@ from .transformer import (MultiheadAttention, TransformerEncoderLayer, Transform
 from .rcda import MultiheadRCDA, rcda_core
 from .position_encoding import PositionEmbeddingSine
 from .detr import DETR, MLP
+from .smca import (GaussianMultiheadAttention, SMCATransformerDecoderLayer, SMCATransformerDecoder, SMCATransformer, smca_core,
+                   dense_gaussian, attention_torch)
 from .resnet import ResNet, build_resnet_backbone, FrozenBatchNorm2d, DeformConv, DeformBottleneckBlock
 from .resnet_vd import ResNetVD, BottleneckVD, build_resnet_vd_backbone
 from .regnet import RegNet, AnyNet, AnyStage, ResBottleneckBlock, BottleneckTransform, SimpleStem, build_regnet_backbone
