@@ -188,8 +188,10 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float* g, int64_t n, co
     s = wave_sum_d(s);
     if (threadIdx.x == 0) {
       const float norm = (float)sqrt(s);
-      float c = max_norm / (norm + 1e-6f);
-      s_coef = c < 1.f ? c : 1.f;
+      const float c = max_norm / (norm + 1e-6f);
+      // as clip_coef_kernel: a NaN norm gives a NaN coefficient (`c < 1 ? c : 1` alone turned it into 1 and the step went
+      // on with unscaled garbage); NaN >= 1 is false, so the early return below lets it through to every gradient
+      s_coef = (norm != norm) ? norm : (c < 1.f ? c : 1.f);
       if (blockIdx.x == 0 && norm_out) *norm_out = norm;
     }
   }
