@@ -728,6 +728,45 @@ typedef struct mi_detr_loss_desc {
 int mi_detr_set_loss_fwd(const mi_detr_loss_desc* d, mi_stream_t s);
 int mi_detr_set_loss_bwd(const mi_detr_loss_desc* d, const float* gw, float* dlogits, float* dboxes, mi_stream_t s);
 
+/* ---- focal set matching and criterion (SMCA-DETR, Anchor DETR) ------------------------
+ * mi_hungarian_match_focal replaces HungarianMatcherSMCA.forward / HungarianMatcherAnchorDETR.forward
+ * (utils/detr_utils.py:119-176, 202-262 - the same computation): mi_hungarian_match with the sigmoid focal class cost
+ * p = sigmoid(logits[label]), cost_class = alpha (1 - p)^2 (-log(p + 1e-8)) - (1 - alpha) p^2 (-log(1 - p + 1e-8))
+ * (the reference fixes alpha = 0.25, gamma = 2).  NC = number of channels (no no-object channel).  Same layouts and limits
+ * (Q, gmax <= 1024).  nmatch[b] = -1 for an image with a NaN / inf cost (scipy raises ValueError there); such an image is
+ * not assigned and its match_q / match_t rows are left as they were. */
+int mi_hungarian_match_focal(const float* logits, const float* boxes, const int64_t* tgt_labels,
+                             const float* tgt_boxes, const int32_t* tgt_off, int B, int Q, int NC, int gmax,
+                             float w_class, float w_bbox, float w_giou, float alpha, float* cost, int64_t* match_q,
+                             int64_t* match_t, int32_t* nmatch, mi_stream_t s);
+/* The set criterion of those two models for the match indices above, forward + backward.
+ * replaces SetCriterion.loss_labels / loss_cardinality / loss_boxes of modeling/meta_arch/smca_detr.py:546-613 and
+ * anchor_detr.py:570-631 and their autograd backward: sigmoid focal loss (detr_seg.py:207-270, gamma 2) over the NC
+ * channels, target 1 only at a matched row's label, summed / num_boxes; alpha < 0 = no alpha weighting.
+ * losses[8] = loss_ce, class_error (100 without a pair), cardinality_error (mean over images of |#rows whose arg max is
+ * not channel NC - 1, minus G_b|: the reference's convention on this head), loss_bbox, loss_giou, 0, matched pairs, 0.
+ * rowstate: caller workspace of B*Q*16 floats, written by fwd and read by bwd.
+ * bwd: gw[3] on device = upstream gradients of (loss_ce, loss_bbox, loss_giou); dlogits [B][Q][NC], dboxes [B][Q][4]
+ * (exactly 0 in rows without a match).  B <= 256. */
+typedef struct mi_focal_loss_desc {
+  const float* logits;
+  const float* boxes;
+  const int64_t* tgt_labels;
+  const float* tgt_boxes;
+  const int32_t* tgt_off;
+  const int64_t* match_q;
+  const int64_t* match_t;
+  const int32_t* nmatch;
+  int32_t B, Q, NC, gmax;
+  float alpha, num_boxes;
+  float* losses;
+  float* rowstate;
+} mi_focal_loss_desc;
+int mi_focal_set_loss_fwd(const mi_focal_loss_desc* d, mi_stream_t s);
+int mi_focal_set_loss_bwd(const mi_focal_loss_desc* d, const float* gw, float* dlogits, float* dboxes, mi_stream_t s);
+/* sizeof(mi_focal_loss_desc) as compiled into the library (binding self-check; mi_abi_sizeof's id list is closed) */
+int mi_focal_loss_desc_sizeof(void);
+
 /* ---- multi-head attention core (DETR, config 4) -------------------------------------
  * O = softmax(scale * Q K^T + key_padding_mask) V per (batch, head); head_dim = 32 (DETR: 256 = 8 x 32).
  * replaces the attention inside nn.MultiheadAttention as called by the transformer layers

@@ -66,6 +66,16 @@ class mi_detr_loss_desc(C.Structure):
     ]
 
 
+class mi_focal_loss_desc(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("boxes", C.c_void_p), ("tgt_labels", C.c_void_p), ("tgt_boxes", C.c_void_p),
+        ("tgt_off", C.c_void_p), ("match_q", C.c_void_p), ("match_t", C.c_void_p), ("nmatch", C.c_void_p),
+        ("B", C.c_int32), ("Q", C.c_int32), ("NC", C.c_int32), ("gmax", C.c_int32),
+        ("alpha", C.c_float), ("num_boxes", C.c_float),
+        ("losses", C.c_void_p), ("rowstate", C.c_void_p),
+    ]
+
+
 class mi_conv_group(C.Structure):
     _fields_ = [("njobs", C.c_int32), ("nblocks", C.c_int32), ("lds_bytes", C.c_int32), ("KC", C.c_int32),
                 ("BN", C.c_int32), ("TPIX", C.c_int32), ("TPS", C.c_int32), ("EPI", C.c_int32),
@@ -412,6 +422,10 @@ _PROTOS = {
     "mi_bn_group_run": (C.c_int, [C.POINTER(mi_bn_group), _vp, _vp]),
     "mi_detr_set_loss_fwd": (C.c_int, [C.POINTER(mi_detr_loss_desc), _vp]),
     "mi_detr_set_loss_bwd": (C.c_int, [C.POINTER(mi_detr_loss_desc), _vp, _vp, _vp, _vp]),
+    "mi_hungarian_match_focal": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "mi_focal_set_loss_fwd": (C.c_int, [C.POINTER(mi_focal_loss_desc), _vp]),
+    "mi_focal_set_loss_bwd": (C.c_int, [C.POINTER(mi_focal_loss_desc), _vp, _vp, _vp, _vp]),
+    "mi_focal_loss_desc_sizeof": (C.c_int, []),
     "mi_mha_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "mi_mha_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "mi_layernorm_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

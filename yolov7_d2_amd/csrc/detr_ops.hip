@@ -21,6 +21,8 @@ struct MatchK {
   const int32_t* toff;   // [B+1]
   int B, Q, NC, gmax;
   float wc, wb, wg;
+  float alpha;           // focal class cost only
+  int guard;             // 1: the cost kernel flagged images with a non-finite cost in nmatch (focal path)
   float* cost;           // [B][Q][gmax]
   int64_t* mq;           // [B][gmax]
   int64_t* mt;           // [B][gmax]
@@ -70,6 +72,50 @@ __global__ __launch_bounds__(64) void match_cost_kernel(const MatchK p) {
   }
 }
 
+// ---- the focal class cost of HungarianMatcherSMCA / HungarianMatcherAnchorDETR (utils/detr_utils.py:143-170, 226-256), same
+// grid and output: p = sigmoid(logit[label]), cost_class = alpha (1 - p)^2 (-log(p + 1e-8)) - (1 - alpha) p^2 (-log(1 - p + 1e-8))
+// in the reference's operation order (gamma = 2 as a product).  Only logit[label] is read: no row statistics.  An image with
+// a NaN / inf cost is flagged in nmatch (zeroed before this launch) - the assignment kernel then leaves it alone.
+__global__ __launch_bounds__(64) void match_cost_focal_kernel(const MatchK p) {
+  const int b = blockIdx.y, q = blockIdx.x, lane = threadIdx.x;
+  const int t0 = p.toff[b], G = p.toff[b + 1] - t0;
+  if (G <= 0) return;
+  const float* lg = p.logits + ((size_t)b * p.Q + q) * p.NC;
+  const float* bx = p.boxes + ((size_t)b * p.Q + q) * 4;
+  const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
+  const float x0 = cx - 0.5f * w, y0 = cy - 0.5f * h, x1 = cx + 0.5f * w, y1 = cy + 0.5f * h;
+  const float area1 = (x1 - x0) * (y1 - y0);
+  const float na = 1.f - p.alpha;
+  for (int g = lane; g < G; g += 64) {
+    const float* tb = p.tbox + (size_t)(t0 + g) * 4;
+    const float tcx = tb[0], tcy = tb[1], tw = tb[2], th = tb[3];
+    const int lab = (int)p.tlab[t0 + g];
+    const float pr = 1.f / (1.f + expf(-lg[lab]));
+    const float om = 1.f - pr;
+    const float neg = na * (pr * pr) * (-logf(om + 1e-8f));
+    const float pos = p.alpha * (om * om) * (-logf(pr + 1e-8f));
+    const float cost_class = pos - neg;
+    float cost_bbox = fabsf(cx - tcx);
+    cost_bbox += fabsf(cy - tcy);
+    cost_bbox += fabsf(w - tw);
+    cost_bbox += fabsf(h - th);
+    const float u0 = tcx - 0.5f * tw, v0 = tcy - 0.5f * th, u1 = tcx + 0.5f * tw, v1 = tcy + 0.5f * th;
+    const float area2 = (u1 - u0) * (v1 - v0);
+    const float iw = fmaxf(fminf(x1, u1) - fmaxf(x0, u0), 0.f), ih = fmaxf(fminf(y1, v1) - fmaxf(y0, v0), 0.f);
+    const float inter = iw * ih;
+    const float uni = area1 + area2 - inter;
+    const float iou = inter / uni;
+    const float ew = fmaxf(fmaxf(x1, u1) - fminf(x0, u0), 0.f), eh = fmaxf(fmaxf(y1, v1) - fminf(y0, v0), 0.f);
+    const float earea = ew * eh;
+    const float giou = iou - (earea - uni) / earea;
+    const float cost_giou = -giou;
+    float c = p.wb * cost_bbox + p.wc * cost_class;
+    c = c + p.wg * cost_giou;
+    p.cost[((size_t)b * p.Q + q) * p.gmax + g] = c;
+    if (!(fabsf(c) <= 3.4028234e38f)) p.nmatch[b] = -1;      // (every writer stores the same value)
+  }
+}
+
 // ---- linear sum assignment, one wave per image
 __global__ __launch_bounds__(64) void lsap_kernel(const MatchK p) {
   __shared__ double u[LSAP_MAXN], v[LSAP_MAXN], sp[LSAP_MAXN];
@@ -83,6 +129,7 @@ __global__ __launch_bounds__(64) void lsap_kernel(const MatchK p) {
   auto cost = [&](int i, int j) -> double {  // i in [0,nr), j in [0,nc)
     return tr ? (double)Cb[(size_t)j * p.gmax + i] : (double)Cb[(size_t)i * p.gmax + j];
   };
+  if (p.guard && p.nmatch[b] < 0) return;   // flagged by match_cost_focal_kernel (block-uniform: one wave, one word)
   if (lane == 0) p.nmatch[b] = nr;
   if (nr <= 0) return;
   for (int k = lane; k < LSAP_MAXN; k += 64) {
@@ -167,10 +214,11 @@ __global__ __launch_bounds__(64) void lsap_kernel(const MatchK p) {
   }
 }
 
-extern "C" int mi_hungarian_match(const float* logits, const float* boxes, const int64_t* tgt_labels,
-                                  const float* tgt_boxes, const int32_t* tgt_off, int B, int Q, int NC, int gmax,
-                                  float w_class, float w_bbox, float w_giou, float* cost, int64_t* match_q,
-                                  int64_t* match_t, int32_t* nmatch, mi_stream_t st) {
+// focal 0: the softmax class cost; 1: the focal one with that alpha, non-finite costs flagged before the assignment
+static int match_launch(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
+                        const int32_t* tgt_off, int B, int Q, int NC, int gmax, float w_class, float w_bbox, float w_giou,
+                        int focal, float alpha, float* cost, int64_t* match_q, int64_t* match_t, int32_t* nmatch,
+                        mi_stream_t st) {
   MI_REQUIRE(logits && boxes && tgt_labels && tgt_boxes && tgt_off && cost && match_q && match_t && nmatch,
              "hungarian_match: null");
   MI_REQUIRE(B > 0 && Q > 0 && Q <= LSAP_MAXN && NC > 0 && gmax > 0 && gmax <= LSAP_MAXN,
@@ -178,13 +226,36 @@ extern "C" int mi_hungarian_match(const float* logits, const float* boxes, const
   MatchK k;
   k.logits = logits; k.boxes = boxes; k.tlab = tgt_labels; k.tbox = tgt_boxes; k.toff = tgt_off;
   k.B = B; k.Q = Q; k.NC = NC; k.gmax = gmax; k.wc = w_class; k.wb = w_bbox; k.wg = w_giou;
+  k.alpha = alpha; k.guard = focal;
   k.cost = cost; k.mq = match_q; k.mt = match_t; k.nmatch = nmatch;
   hipStream_t s = (hipStream_t)st;
-  hipLaunchKernelGGL(match_cost_kernel, dim3(Q, B), dim3(64), 0, s, k);
+  if (focal) {
+    if (hipMemsetAsync(nmatch, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess) MI_FAIL(MI_ELAUNCH, "hungarian_match_focal: memset");
+    hipLaunchKernelGGL(match_cost_focal_kernel, dim3(Q, B), dim3(64), 0, s, k);
+  } else {
+    hipLaunchKernelGGL(match_cost_kernel, dim3(Q, B), dim3(64), 0, s, k);
+  }
   MI_CHECK_LAUNCH("match_cost");
   hipLaunchKernelGGL(lsap_kernel, dim3(B), dim3(64), 0, s, k);
   MI_CHECK_LAUNCH("lsap");
   return MI_OK;
+}
+
+extern "C" int mi_hungarian_match(const float* logits, const float* boxes, const int64_t* tgt_labels,
+                                  const float* tgt_boxes, const int32_t* tgt_off, int B, int Q, int NC, int gmax,
+                                  float w_class, float w_bbox, float w_giou, float* cost, int64_t* match_q,
+                                  int64_t* match_t, int32_t* nmatch, mi_stream_t st) {
+  return match_launch(logits, boxes, tgt_labels, tgt_boxes, tgt_off, B, Q, NC, gmax, w_class, w_bbox, w_giou, 0, 0.f, cost,
+                      match_q, match_t, nmatch, st);
+}
+
+// the same matching with the sigmoid focal class cost (SMCA-DETR, Anchor DETR); NC = number of channels
+extern "C" int mi_hungarian_match_focal(const float* logits, const float* boxes, const int64_t* tgt_labels,
+                                        const float* tgt_boxes, const int32_t* tgt_off, int B, int Q, int NC, int gmax,
+                                        float w_class, float w_bbox, float w_giou, float alpha, float* cost,
+                                        int64_t* match_q, int64_t* match_t, int32_t* nmatch, mi_stream_t st) {
+  return match_launch(logits, boxes, tgt_labels, tgt_boxes, tgt_off, B, Q, NC, gmax, w_class, w_bbox, w_giou, 1, alpha, cost,
+                      match_q, match_t, nmatch, st);
 }
 
 // assignment only, on a caller-provided cost matrix [B][Q][gmax] with ng[b] valid columns (tests, other matchers)

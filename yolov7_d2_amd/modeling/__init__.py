@@ -5,6 +5,8 @@ from .yolox import YOLOX
 from .yolox_net import CSPDarknet, YOLOPAFPN, YOLOXHead, build_cspdarknetx_backbone
 from .detr_matcher import HungarianMatcher
 from .detr_criterion import SetCriterion
+from .focal_criterion import (FocalSetCriterion, HungarianMatcherAnchorDETR, HungarianMatcherFocal, HungarianMatcherSMCA,
+                              SMCASetCriterion)
 from .attention import mha_core
 from .iou_loss import IOUlossV6, IOUloss, pairwise_bbox_iou, bboxes_iou
 from .transformer import (MultiheadAttention, TransformerEncoderLayer, TransformerDecoderLayer, TransformerEncoder,

@@ -18,37 +18,49 @@ from .. import _lib as L
 from .detr_matcher import HungarianMatcher, PackedTargets
 
 
+def set_loss_forward(ctx, logits, boxes, m, coef, num_boxes, abi):
+    """the forward of both set criteria (this file's and focal_criterion's): abi = (descriptor struct, the name of its one
+    own field - eos_coef / alpha -, the fwd and the bwd entry point)"""
+    desc, field, fwd, bwd = abi
+    lg = logits.detach().float().contiguous()
+    bx = boxes.detach().float().contiguous()
+    B, Q, NC = lg.shape
+    dev = lg.device
+    losses = torch.empty(8, dtype=torch.float32, device=dev)
+    rows = torch.empty(B * Q * 16, dtype=torch.float32, device=dev)
+    d = getattr(L, desc)()
+    d.logits, d.boxes = lg.data_ptr(), bx.data_ptr()
+    d.tgt_labels, d.tgt_boxes, d.tgt_off = m["tgt_labels"].data_ptr(), m["tgt_boxes"].data_ptr(), m["tgt_off"].data_ptr()
+    d.match_q, d.match_t, d.nmatch = m["match_q"].data_ptr(), m["match_t"].data_ptr(), m["nmatch"].data_ptr()
+    d.B, d.Q, d.NC, d.gmax = B, Q, NC, m["gmax"]
+    setattr(d, field, float(coef))
+    d.num_boxes = float(num_boxes)
+    d.losses, d.rowstate = losses.data_ptr(), rows.data_ptr()
+    L.check(getattr(L.lib(), fwd)(C.byref(d), L.stream_ptr()), fwd)
+    ctx.desc, ctx.keep, ctx.bwd = d, (lg, bx, m, losses, rows), bwd
+    ctx.in_dtypes = (logits.dtype, boxes.dtype)
+    return losses[:5].clone()
+
+
+def set_loss_backward(ctx, g):
+    lg, bx = ctx.keep[0], ctx.keep[1]
+    gw = torch.stack((g[0], g[3], g[4])).float().contiguous()     # (no index tensor: nothing is copied from the host)
+    dl, db = torch.empty_like(lg), torch.empty_like(bx)
+    L.check(getattr(L.lib(), ctx.bwd)(C.byref(ctx.desc), gw.data_ptr(), dl.data_ptr(), db.data_ptr(), L.stream_ptr()), ctx.bwd)
+    return dl.to(ctx.in_dtypes[0]), db.to(ctx.in_dtypes[1]), None, None, None
+
+
 class _SetLossFn(torch.autograd.Function):
     """(logits, boxes) -> tensor[5] = loss_ce, class_error, cardinality_error, loss_bbox, loss_giou"""
 
     @staticmethod
     def forward(ctx, logits, boxes, m, eos_coef, num_boxes):
-        lg = logits.detach().float().contiguous()
-        bx = boxes.detach().float().contiguous()
-        B, Q, NC = lg.shape
-        dev = lg.device
-        losses = torch.empty(8, dtype=torch.float32, device=dev)
-        rows = torch.empty(B * Q * 16, dtype=torch.float32, device=dev)
-        d = L.mi_detr_loss_desc()
-        d.logits, d.boxes = lg.data_ptr(), bx.data_ptr()
-        d.tgt_labels, d.tgt_boxes, d.tgt_off = m["tgt_labels"].data_ptr(), m["tgt_boxes"].data_ptr(), m["tgt_off"].data_ptr()
-        d.match_q, d.match_t, d.nmatch = m["match_q"].data_ptr(), m["match_t"].data_ptr(), m["nmatch"].data_ptr()
-        d.B, d.Q, d.NC, d.gmax = B, Q, NC, m["gmax"]
-        d.eos_coef, d.num_boxes = float(eos_coef), float(num_boxes)
-        d.losses, d.rowstate = losses.data_ptr(), rows.data_ptr()
-        L.check(L.lib().mi_detr_set_loss_fwd(C.byref(d), L.stream_ptr()), "mi_detr_set_loss_fwd")
-        ctx.desc, ctx.keep = d, (lg, bx, m, losses, rows)
-        ctx.in_dtypes = (logits.dtype, boxes.dtype)
-        return losses[:5].clone()
+        return set_loss_forward(ctx, logits, boxes, m, eos_coef, num_boxes,
+                                ("mi_detr_loss_desc", "eos_coef", "mi_detr_set_loss_fwd", "mi_detr_set_loss_bwd"))
 
     @staticmethod
     def backward(ctx, g):
-        lg, bx = ctx.keep[0], ctx.keep[1]
-        gw = torch.stack((g[0], g[3], g[4])).float().contiguous()     # (no index tensor: nothing is copied from the host)
-        dl, db = torch.empty_like(lg), torch.empty_like(bx)
-        L.check(L.lib().mi_detr_set_loss_bwd(C.byref(ctx.desc), gw.data_ptr(), dl.data_ptr(), db.data_ptr(),
-                                             L.stream_ptr()), "mi_detr_set_loss_bwd")
-        return dl.to(ctx.in_dtypes[0]), db.to(ctx.in_dtypes[1]), None, None, None
+        return set_loss_backward(ctx, g)
 
 
 def _pack_indices(indices, targets, dev):
@@ -89,16 +101,32 @@ class SetCriterion(nn.Module):
             return self.matcher.match_device(outputs, targets)
         return _pack_indices(self.matcher(outputs, targets), targets, outputs["pred_logits"].device)
 
-    def _level(self, outputs, targets, num_boxes, log, inv_nb=None):
-        if not outputs["pred_logits"].is_cuda:
+    # what a criterion with another classification loss (focal_criterion.FocalSetCriterion) changes: the channel count of
+    # the head, the loss kernels, and whether loss_ce is a sum over num_boxes (then the packed paths, whose kernels run with
+    # num_boxes = 1, scale it by 1 / num_boxes like the two box losses)
+    channels_extra, ce_per_box = 1, False
+
+    def _set_loss(self, logits, boxes, m, num_boxes):
+        return _SetLossFn.apply(logits, boxes, m, self.eos_coef, num_boxes)
+
+    @staticmethod
+    def _weigh(V, w, s):
+        """[levels, 5] raw values x weights x the 1 / num_boxes scales of weighted_packed"""
+        return V * (w * s)
+
+    def _check_level(self, lv):
+        if not lv["pred_logits"].is_cuda:
             raise L.MI355Error("SetCriterion: the MI355X path needs device tensors (no CPU fallback)")
-        if outputs["pred_logits"].shape[-1] != self.num_classes + 1:
-            raise ValueError("pred_logits must have num_classes + 1 channels")
+        if lv["pred_logits"].shape[-1] != self.num_classes + self.channels_extra:
+            raise ValueError("pred_logits must have num_classes%s channels" % (" + 1" if self.channels_extra else ""))
+
+    def _level(self, outputs, targets, num_boxes, log, inv_nb=None):
+        self._check_level(outputs)
         m = self._match(outputs, targets)
-        v = _SetLossFn.apply(outputs["pred_logits"], outputs["pred_boxes"], m, self.eos_coef, num_boxes)
+        v = self._set_loss(outputs["pred_logits"], outputs["pred_boxes"], m, num_boxes)
         out = {}
         if "labels" in self.losses:
-            out["loss_ce"] = v[0]
+            out["loss_ce"] = v[0] * inv_nb[0] if (inv_nb is not None and self.ce_per_box) else v[0]
             if log:
                 out["class_error"] = v[1].detach()
         if "cardinality" in self.losses:
@@ -117,10 +145,7 @@ class SetCriterion(nn.Module):
         inv = targets.inv_num_boxes
         levels = [{k: v for k, v in outputs.items() if k != "aux_outputs"}] + list(outputs.get("aux_outputs", []))
         for lv in levels:
-            if not lv["pred_logits"].is_cuda:
-                raise L.MI355Error("SetCriterion: the MI355X path needs device tensors (no CPU fallback)")
-            if lv["pred_logits"].shape[-1] != self.num_classes + 1:
-                raise ValueError("pred_logits must have num_classes + 1 channels")
+            self._check_level(lv)
         lvt = getattr(targets, "lv", None)
         import os
         if (isinstance(self.matcher, HungarianMatcher) and lvt is not None and lvt["n"] == len(levels)
@@ -128,7 +153,7 @@ class SetCriterion(nn.Module):
             ms = self.matcher.match_device_levels(levels, targets)          # all levels: one cost + one assignment launch
         else:
             ms = [self._match(lv, targets) for lv in levels]
-        vs = [_SetLossFn.apply(lv["pred_logits"], lv["pred_boxes"], m, self.eos_coef, 1.0) for lv, m in zip(levels, ms)]
+        vs = [self._set_loss(lv["pred_logits"], lv["pred_boxes"], m, 1.0) for lv, m in zip(levels, ms)]
         V = torch.stack(vs)                                               # [levels, 5]: ce, class_error, cardinality, bbox, giou
         names = ("loss_ce", "class_error", "cardinality_error", "loss_bbox", "loss_giou")
         need = ("labels", "labels", "cardinality", "boxes", "boxes")
@@ -138,10 +163,11 @@ class SetCriterion(nn.Module):
             sfx = [""] + [f"_{i}" for i in range(len(levels) - 1)]
             w = torch.tensor([[float(self.weight_dict.get(n + s_, 1.0)) for n in names] for s_ in sfx])
             m = torch.tensor([[float(n + s_ in self.weight_dict and q in self.losses) for n, q in zip(names, need)] for s_ in sfx])
-            a, b = torch.tensor([1.0, 1.0, 1.0, 0.0, 0.0]), torch.tensor([0.0, 0.0, 0.0, 1.0, 1.0])
+            b = torch.tensor([1.0 if self.ce_per_box else 0.0, 0.0, 0.0, 1.0, 1.0])
+            a = 1.0 - b
             c = self.__dict__["_packed_consts"] = (key, w.to(V.device), m.to(V.device), a.to(V.device), b.to(V.device), sfx)
         _, w, m, a, b, sfx = c
-        R = V * (w * torch.addcmul(a, b, inv[0]))                         # bbox / giou sums ran with num_boxes = 1 (linear in 1 / n)
+        R = self._weigh(V, w, torch.addcmul(a, b, inv[0]))                # bbox / giou sums ran with num_boxes = 1 (linear in 1 / n)
         out = {}
         for l_, s_ in enumerate(sfx):
             for j, (n, q) in enumerate(zip(names, need)):

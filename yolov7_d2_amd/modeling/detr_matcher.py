@@ -48,6 +48,13 @@ class HungarianMatcher(nn.Module):
         self.cost_class, self.cost_bbox, self.cost_giou = cost_class, cost_bbox, cost_giou
         assert cost_class != 0 or cost_bbox != 0 or cost_giou != 0, "all costs cant be 0"
 
+    def _launch(self, logits, boxes, tl, tb, off, bs, nq, nc, gmax, cost, mq, mt, nm, what):
+        """cost matrix + assignment of `bs` images (the one thing a matcher with another class cost overrides)"""
+        L.check(L.lib().mi_hungarian_match(logits.data_ptr(), boxes.data_ptr(), tl.data_ptr(), tb.data_ptr(),
+                                           off.data_ptr(), bs, nq, nc, gmax, float(self.cost_class),
+                                           float(self.cost_bbox), float(self.cost_giou), cost.data_ptr(), mq.data_ptr(),
+                                           mt.data_ptr(), nm.data_ptr(), L.stream_ptr()), "mi_hungarian_match" + what)
+
     @torch.no_grad()
     def match_device(self, outputs, targets):
         """the matching without any host round trip: returns a dict of device tensors (match_q / match_t int64
@@ -73,10 +80,7 @@ class HungarianMatcher(nn.Module):
         mq = torch.empty(bs, gmax, dtype=torch.int64, device=dev)
         mt = torch.empty(bs, gmax, dtype=torch.int64, device=dev)
         nm = torch.zeros(bs, dtype=torch.int32, device=dev)
-        L.check(L.lib().mi_hungarian_match(logits.data_ptr(), boxes.data_ptr(), tl.data_ptr(), tb.data_ptr(),
-                                           off.data_ptr(), bs, nq, nc, gmax, float(self.cost_class),
-                                           float(self.cost_bbox), float(self.cost_giou), cost.data_ptr(), mq.data_ptr(),
-                                           mt.data_ptr(), nm.data_ptr(), L.stream_ptr()), "mi_hungarian_match")
+        self._launch(logits, boxes, tl, tb, off, bs, nq, nc, gmax, cost, mq, mt, nm, "")
         self.last_cost = cost
         return dict(match_q=mq, match_t=mt, nmatch=nm, tgt_off=off, tgt_labels=tl, tgt_boxes=tb, gmax=gmax,
                     num_targets=ntot)
@@ -101,10 +105,7 @@ class HungarianMatcher(nn.Module):
         mq = torch.empty(n * bs, gmax, dtype=torch.int64, device=dev)
         mt = torch.empty(n * bs, gmax, dtype=torch.int64, device=dev)
         nm = torch.zeros(n * bs, dtype=torch.int32, device=dev)
-        L.check(L.lib().mi_hungarian_match(logits.data_ptr(), boxes.data_ptr(), lv["labels"].data_ptr(), lv["boxes"].data_ptr(),
-                                           lv["off"].data_ptr(), n * bs, nq, nc, gmax, float(self.cost_class),
-                                           float(self.cost_bbox), float(self.cost_giou), cost.data_ptr(), mq.data_ptr(),
-                                           mt.data_ptr(), nm.data_ptr(), L.stream_ptr()), "mi_hungarian_match (all levels)")
+        self._launch(logits, boxes, lv["labels"], lv["boxes"], lv["off"], n * bs, nq, nc, gmax, cost, mq, mt, nm, " (all levels)")
         self.last_cost = cost[:bs]
         return [dict(match_q=mq[l * bs:(l + 1) * bs], match_t=mt[l * bs:(l + 1) * bs], nmatch=nm[l * bs:(l + 1) * bs],
                      tgt_off=targets.tgt_off, tgt_labels=targets.tgt_labels, tgt_boxes=targets.tgt_boxes, gmax=gmax,
