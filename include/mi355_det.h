@@ -767,6 +767,28 @@ int mi_focal_set_loss_bwd(const mi_focal_loss_desc* d, const float* gw, float* d
 /* sizeof(mi_focal_loss_desc) as compiled into the library (binding self-check; mi_abi_sizeof's id list is closed) */
 int mi_focal_loss_desc_sizeof(void);
 
+/* ---- focal top-k postprocess and the SMCA box head tail (SMCA-DETR, Anchor DETR) ------------------------
+ * mi_focal_topk_postprocess replaces SMCADetr.inference (meta_arch/smca_detr.py:216-264) + detector_postprocess, and
+ * PostProcess of anchor_detr.py, for the whole batch in one launch (one block per image).
+ * logits fp32 [B][Q][C]; boxes fp32 [B][Q][4] normalised cxcywh; sizes_dev int64 [B][2] = (h, w) of each image on the device;
+ * out_sizes int64 [B][2] = (out_h, out_w) on the device, or NULL.  Per image the K entries with the largest logit win (the
+ * sigmoid is monotonic), ties towards the lower flat index q * C + c, -0 == +0, NaN greatest (as torch.topk), +-inf ordinary.
+ * Output position 0 is the best; positions descend by (logit, then ascending index).  scores [B][K] = sigmoid(logit),
+ * labels int64 [B][K] = idx % C, query int32 [B][K] = idx / C, boxes_xyxy [B][K][4] =
+ * (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h) * (w_img, h_img, w_img, h_img); with out_sizes then * (float) (out_w / w_img),
+ * (float) (out_h / h_img) (quotients in double, as detector_postprocess forms them) and clamped to [0, out_w] x [0, out_h].
+ * No float atomics, a pure function of its inputs.  Refused (MI_EINVAL, nothing launched): K > Q * C (torch.topk raises),
+ * K > 1024, Q * C >= 2^31. */
+int mi_focal_topk_postprocess(const float* logits, const float* boxes, const int64_t* sizes_dev, const int64_t* out_sizes,
+                              int B, int Q, int C, int K, float* scores, int64_t* labels, int32_t* query, float* boxes_xyxy,
+                              mi_stream_t s);
+/* y[l][b][q][:] = sigmoid(x[l][b][q][:] + (p[b][q][0], p[b][q][1], 0, 0)): the SMCA box head (smca_detr.py:500-503); x, y fp32
+ * [L][B][Q][4], p fp32 [B][Q][2] broadcast over the L decoder levels.
+ * bwd: dx = dy * y * (1 - y) with y recomputed from x + p; dp[b][q][j] = sum over l ascending of dx[l][b][q][j] in fp32, one
+ * thread per (b, q): no atomics, bit-reproducible. */
+int mi_box_ref_sigmoid_fwd(const float* x, const float* p, float* y, int L, int B, int Q, mi_stream_t s);
+int mi_box_ref_sigmoid_bwd(const float* x, const float* p, const float* dy, float* dx, float* dp, int L, int B, int Q, mi_stream_t s);
+
 /* ---- multi-head attention core (DETR, config 4) -------------------------------------
  * O = softmax(scale * Q K^T + key_padding_mask) V per (batch, head); head_dim = 32 (DETR: 256 = 8 x 32).
  * replaces the attention inside nn.MultiheadAttention as called by the transformer layers

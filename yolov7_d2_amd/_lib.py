@@ -426,6 +426,9 @@ _PROTOS = {
     "mi_focal_set_loss_fwd": (C.c_int, [C.POINTER(mi_focal_loss_desc), _vp]),
     "mi_focal_set_loss_bwd": (C.c_int, [C.POINTER(mi_focal_loss_desc), _vp, _vp, _vp, _vp]),
     "mi_focal_loss_desc_sizeof": (C.c_int, []),
+    "mi_focal_topk_postprocess": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mi_box_ref_sigmoid_fwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mi_box_ref_sigmoid_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mi_mha_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "mi_mha_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "mi_layernorm_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

@@ -233,6 +233,54 @@ def detr_r50_cfg(device="cuda", **over):
     return cfg
 
 
+def smca_detr_cfg(device="cuda", **over):
+    """the settings of configs/coco/detr/smcadetr_origin.yaml without needing the file"""
+    cfg = add_yolo_config(get_cfg())
+    cfg.MODEL.DEVICE = device
+    cfg.MODEL.META_ARCHITECTURE = "SMCADetr"
+    cfg.MODEL.PIXEL_MEAN = [123.675, 116.280, 103.530]
+    cfg.MODEL.PIXEL_STD = [58.395, 57.120, 57.375]
+    cfg.MODEL.MASK_ON = False
+    cfg.MODEL.BACKBONE.NAME = "build_resnet_backbone"
+    cfg.MODEL.RESNETS.DEPTH = 50
+    cfg.MODEL.RESNETS.STRIDE_IN_1X1 = False
+    cfg.MODEL.RESNETS.OUT_FEATURES = ["res2", "res3", "res4", "res5"]
+    cfg.MODEL.DETR.GIOU_WEIGHT, cfg.MODEL.DETR.L1_WEIGHT = 2.0, 5.0
+    cfg.MODEL.DETR.NUM_OBJECT_QUERIES = 300
+    cfg.MODEL.DETR.DIM_FEEDFORWARD = 2048
+    cfg.MODEL.DETR.DROPOUT = 0.1
+    cfg.MODEL.DETR.ENC_LAYERS = cfg.MODEL.DETR.DEC_LAYERS = 6
+    cfg.MODEL.DETR.HIDDEN_DIM = 256
+    cfg.MODEL.DETR.NUM_CLASSES = 80
+    cfg.MODEL.DETR.NUM_FEATURE_LEVELS = 1
+    cfg.MODEL.YOLO.CONF_THRESHOLD = 0.0001
+    cfg.MODEL.YOLO.IGNORE_THRESHOLD = 0.001
+    cfg.SOLVER.AMP.ENABLED = True
+    cfg.SOLVER.IMS_PER_BATCH = 16
+    cfg.SOLVER.BASE_LR = 0.0001
+    cfg.SOLVER.STEPS = (325720,)
+    cfg.SOLVER.MAX_ITER = 409650
+    cfg.SOLVER.WARMUP_FACTOR = 1.0
+    cfg.SOLVER.WARMUP_ITERS = 10
+    cfg.SOLVER.WEIGHT_DECAY = 0.0001
+    cfg.SOLVER.OPTIMIZER = "ADAMW"
+    cfg.SOLVER.LR_MULTIPLIER_OVERWRITE = [{"backbone": 0.1}, {"reference_points": 0.1, "sampling_offsets": 0.1}]
+    cfg.SOLVER.CLIP_GRADIENTS.ENABLED = True
+    cfg.SOLVER.CLIP_GRADIENTS.CLIP_TYPE = "full_model"
+    cfg.SOLVER.CLIP_GRADIENTS.CLIP_VALUE = 0.1
+    cfg.INPUT.MIN_SIZE_TRAIN = (480, 512, 544, 576, 608, 640, 672, 704, 736, 768, 800)
+    cfg.INPUT.CROP.ENABLED = True
+    cfg.INPUT.CROP.TYPE = "absolute_range"
+    cfg.INPUT.CROP.SIZE = (384, 600)
+    cfg.INPUT.FORMAT = "RGB"
+    cfg.TEST.EVAL_PERIOD = 7393
+    cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS = False
+    cfg.DATALOADER.NUM_WORKERS = 2
+    for k, v in over.items():
+        cfg.merge_from_list([k, v])
+    return cfg
+
+
 def get_yolox_cfg(config_file=None, opts=()):
     cfg = add_yolo_config(get_cfg())
     if config_file:

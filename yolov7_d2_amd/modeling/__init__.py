@@ -22,6 +22,8 @@ from .regnet import RegNet, AnyNet, AnyStage, ResBottleneckBlock, BottleneckTran
 from .box_ops import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh, box_iou, generalized_box_iou
 from .detr_meta import (Detr, Joiner, MaskedBackbone, MaskedBackboneTraceFriendly, NestedTensor, PostProcess,
                         nested_tensor_from_tensor_list)
+from .smca_detr import (SMCADetr, SMCADETR, MaskedBackboneRes5, TopK, bias_init_with_prob, box_ref_sigmoid, focal_topk_postprocess,
+                        inference_torch)
 from .sparseinst import (SparseInst, InstanceContextEncoder, PyramidPoolingModule, MyAdaptiveAvgPool2d, InstanceBranch,
                          GroupInstanceBranch, MaskBranch, BaseIAMDecoder, GroupIAMDecoder, SparseInstCriterion,
                          SparseInstMatcher, build_sparse_inst_encoder, build_sparse_inst_decoder,
